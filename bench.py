@@ -15,9 +15,17 @@ batch) and merged on the device (lance_hip_merge_topk_device).
                    rows for the same B queries ("scaling": "strong").
 --config nstar is the north_star target: flat L2 over 10M x 768 f32.
 
-Prints ONE JSON line on rank 0 (driver contract).  The CPU baseline (rank 0,
-N = 1 only) times oracle/flat_knn.c — the port of the reference's flat search
-(rust_lib/src/lance_manager.rs:393-451 -> lance flat KNN) — on a bounded sample.
+Prints ONE JSON line on rank 0 (driver contract).  A plain run does only what
+`value` / `ms_per_step` need: build the store, settle, warm up, time the K
+steps, print.  --full adds every other leg and check (recall against the
+oracle, the CPU baseline, the synchronous / host-buffer / other-scaling legs,
+the kernel-time roofline); the --no-* switches trim that set.  The CPU baseline
+(rank 0, N = 1 only) times oracle/flat_knn.c — the port of the reference's flat
+search (rust_lib/src/lance_manager.rs:393-451 -> lance flat KNN) — on a bounded
+sample.
+--dump-outputs DIR writes what the last timed step returned (labels, distances,
+counts) as DIR/<name>.npy; inputs are seeded, so two builds compare array for
+array.
 """
 from __future__ import annotations
 
@@ -80,6 +88,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: recall and exactness against the CPU oracle, the CPU baseline, the "
+                         "synchronous / host-buffer / other-scaling legs and the kernel-time roofline (the --no-* "
+                         "switches trim that set); default: the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (labels as float64, "
+                         "distances and counts as float32) to DIR/labels.npy, DIR/distances.npy, DIR/counts.npy")
     ap.add_argument("--settle-s", type=float, default=0.3,
                     help="untimed steps for about this long BEFORE the W warmup steps: the GPU clocks up over its "
                          "first ~40-60 steps under load (C2 0.34 -> 0.27 ms per step, tools/ramp_probe.py, "
@@ -148,6 +163,8 @@ def parse():
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
                     help="extra index option (lance_hip_set_option), repeatable, e.g. --opt scan_i8=off")
     a = ap.parse_args()
+    if not a.full:  # a plain run: the timed steps only
+        a.no_cpu_baseline = a.no_recall = a.no_host_batch = a.no_sync_leg = a.no_other_scaling = True
     for key, v in CONFIGS[a.config].items():
         if getattr(a, key, None) is None:
             setattr(a, key, v)
@@ -246,6 +263,17 @@ def timed_steps(step, steps, warmup, dist, device, sync):
     if dist:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     return float(elapsed.item()), res, np.diff(np.array([t0] + marks)) * 1e3
+
+
+def dump_outputs(dirname, res):
+    """--dump-outputs: the arrays the last timed step returned to its caller —
+    (labels, distances[, counts]) — as DIR/<name>.npy; labels as float64 (exact
+    below 2^53), the rest as float32.  A few KB per file for every config."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, x, dt in zip(("labels", "distances", "counts"), res, (np.float64, np.float32, np.float32)):
+        if torch.is_tensor(x):
+            x = x.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(x).astype(dt))
 
 
 def main_dry_run(a):
@@ -560,6 +588,8 @@ def main_ivf(a):
     t = float(elapsed.item())
     if pipelined:
         res = tuple(x.clone() for x in last_out[0])
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, res)
     sync_leg = None
     if pipelined and world == 1 and not a.no_sync_leg:
         # the synchronous call beside it (one lance_hip_search_batch_device per batch)
@@ -569,12 +599,14 @@ def main_ivf(a):
                     "ms_per_step": round(1000.0 * ts / a.steps, 4),
                     "api": "lance_hip_search_batch_device, one synchronous call per batch",
                     "ids_equal_pipelined": bool(np.array_equal(rs[0].cpu().numpy(), res[0].cpu().numpy()))}
-    lance_hip.LanceHipSetOption(h, "time_kernels", "1")
-    for _ in range(max(3, min(a.steps, 10))):
-        step()
-    torch.cuda.synchronize()
-    kt = lance_hip.LanceHipKernelTimes(h)
-    lance_hip.LanceHipSetOption(h, "time_kernels", "0")
+    kt = None
+    if a.full:
+        lance_hip.LanceHipSetOption(h, "time_kernels", "1")
+        for _ in range(max(3, min(a.steps, 10))):
+            step()
+        torch.cuda.synchronize()
+        kt = lance_hip.LanceHipKernelTimes(h)
+        lance_hip.LanceHipSetOption(h, "time_kernels", "0")
     res_l = res[0].cpu().numpy()
 
     # the list-major 8-bit-LUT scan runs for m <= 96 and k * refine <= 512 (ivf.h FQ_MAX_M / FQ_MAX_KK)
@@ -635,7 +667,7 @@ def main_ivf(a):
     if rank == 0:
         value = BG * a.steps / t
         roof = None
-        if kt["ivf_scan_launches"] > 0:
+        if kt and kt["ivf_scan_launches"] > 0:
             avg_ms = kt["ivf_scan_ms_total"] / kt["ivf_scan_launches"]
             bytes_launch = kt["ivf_scan_bytes"] / kt["ivf_scan_launches"]
             ach = bytes_launch / (avg_ms * 1e-3) / 1e9
@@ -707,26 +739,36 @@ def main_c1(a):
     for i in range(a.warmup):
         lance_hip.LanceDetachedSearch(h, Q[i % len(Q)], D, K)
     got = []
+    last = None
     t0 = time.perf_counter()
     for i in range(a.steps):
-        got.append(lance_hip.LanceDetachedSearch(h, Q[i % len(Q)], D, K)[0])
+        last = lance_hip.LanceDetachedSearch(h, Q[i % len(Q)], D, K)
+        got.append(last[0])
     t = time.perf_counter() - t0
-    lance_hip.LanceHipSetOption(h, "time_kernels", "1")
-    for i in range(10):
-        lance_hip.LanceDetachedSearch(h, Q[i], D, K)
-    kt = lance_hip.LanceHipKernelTimes(h)
-    small = lance_hip.LanceHipLastSearchStats(h)["small_exact"]
-    nthreads = cpu_threads(a)
-    nr = min(16, a.steps)
-    el, _, _ = c_oracle.flat_search_batch(X, Q[:nr], K, a.metric, acc64=True, nthreads=nthreads)
-    exact = all((got[i] == el[i]).all() for i in range(nr))
-    done, tc0 = 0, time.perf_counter()
-    while time.perf_counter() - tc0 < min(a.cpu_seconds, 5.0) or done < 2:
-        c_oracle.flat_search_batch(X, Q[done % len(Q):done % len(Q) + 1], K, a.metric, acc64=False, nthreads=nthreads)
-        done += 1
-    tcpu = time.perf_counter() - tc0
+    if a.dump_outputs and last is not None:
+        dump_outputs(a.dump_outputs, last)
+    kt = exact = cpu = None
+    if a.full:
+        lance_hip.LanceHipSetOption(h, "time_kernels", "1")
+        for i in range(10):
+            lance_hip.LanceDetachedSearch(h, Q[i], D, K)
+        kt = lance_hip.LanceHipKernelTimes(h)
+        small = lance_hip.LanceHipLastSearchStats(h)["small_exact"]
+        nthreads = cpu_threads(a)
+        nr = min(16, a.steps)
+        el, _, _ = c_oracle.flat_search_batch(X, Q[:nr], K, a.metric, acc64=True, nthreads=nthreads)
+        exact = all((got[i] == el[i]).all() for i in range(nr))
+        done, tc0 = 0, time.perf_counter()
+        while time.perf_counter() - tc0 < min(a.cpu_seconds, 5.0) or done < 2:
+            c_oracle.flat_search_batch(X, Q[done % len(Q):done % len(Q) + 1], K, a.metric, acc64=False,
+                                       nthreads=nthreads)
+            done += 1
+        tcpu = time.perf_counter() - tc0
+        cpu = {"value": done / tcpu, "unit": "queries/s", "cores": nthreads, "kind": "port",
+               "sample": f"{done} queries, one per call, exact f32 l2 over {N}x{D} "
+                         f"({tcpu:.1f} s, oracle/flat_knn.c, {nthreads} OpenMP threads)"}
     roof = None
-    if kt["dense_launches"]:
+    if kt and kt["dense_launches"]:
         ms = kt["dense_ms_total"] / kt["dense_launches"]
         ld = ((D + 63) // 64) * 64
         if small:
@@ -748,10 +790,7 @@ def main_c1(a):
             "vs_baseline": None, "dtype": "f32", "data": "synthetic N(0,1) rows and queries (numpy default_rng)",
             "config": {"workload": "C1 flat l2 10000x128 f32 k=10, lance_detached_search per query (host buffers)",
                        "n": N, "dim": D, "k": K, "global_batch": 1, "parallelism": "single"},
-            "exact_ids": exact, "roofline": roof,
-            "cpu_baseline": {"value": done / tcpu, "unit": "queries/s", "cores": nthreads, "kind": "port",
-                             "sample": f"{done} queries, one per call, exact f32 l2 over {N}x{D} "
-                                       f"({tcpu:.1f} s, oracle/flat_knn.c, {nthreads} OpenMP threads)"}}
+            "exact_ids": exact, "roofline": roof, "cpu_baseline": cpu}
     print(json.dumps(line), flush=True)
     lance_hip.LanceFreeDetached(h)
 
@@ -889,6 +928,8 @@ def main():
         res = last_out[0]
     if a.api == "device":  # (the output buffers are reused by the legs below)
         res = tuple(x.clone() for x in res)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, res)
     st = lance_hip.LanceHipLastSearchStats(h)
     print(f"[bench] per-step ms: min {per.min():.4f} median {np.median(per):.4f} max {per.max():.4f}", file=sys.stderr)
     # extra legs (never `value`): the other multi-GPU scaling mode, and at N = 1
@@ -907,7 +948,7 @@ def main():
                  "rows_per_gpu": n_local}
         del Qo
     syncleg = None
-    if pipelined:
+    if pipelined and a.full:
         ts, rs, _ = timed_steps(lambda: searcher.search(Q, K, reuse_outputs=True), a.steps, a.warmup, dist, dev,
                                 torch.cuda.synchronize)
         syncleg = {"value": round(BG * a.steps / ts, 1), "unit": "queries/s", "ms_per_step": round(1000.0 * ts / a.steps, 4),
@@ -922,12 +963,14 @@ def main():
                  "ids_equal_device": bool((rh[0] == res[0].cpu().numpy()).all())}
     # the scan kernel's own duration (HIP events on the stream it runs on),
     # from separate steps so the event calls stay out of the timed loop above
-    lance_hip.LanceHipSetOption(h, "time_kernels", "1")
-    for _ in range(max(3, min(a.steps, 10))):
-        step()
-    sync()
-    kt = lance_hip.LanceHipKernelTimes(h)
-    lance_hip.LanceHipSetOption(h, "time_kernels", "0")
+    kt = None
+    if a.full:
+        lance_hip.LanceHipSetOption(h, "time_kernels", "1")
+        for _ in range(max(3, min(a.steps, 10))):
+            step()
+        sync()
+        kt = lance_hip.LanceHipKernelTimes(h)
+        lance_hip.LanceHipSetOption(h, "time_kernels", "0")
     if a.api == "device":
         res_l = res[0].cpu().numpy()
         res_d = res[1].cpu().numpy()
@@ -993,7 +1036,7 @@ def main():
         ms_step = 1000.0 * t / a.steps
         value = (1 if a.api == "per_call" else BG) * a.steps / t
         roof = None
-        if kt["scan_launches"] > 0:
+        if kt and kt["scan_launches"] > 0:
             ld = ((D + 63) // 64) * 64
             esz = kt.get("scan_elem_bytes") or (2 if a.storage == "bf16" else 4)
             avg_ms = kt["scan_ms_total"] / kt["scan_launches"]
@@ -1078,12 +1121,14 @@ def main():
         if pipelined and inproc_devs:
             line["config"]["pipeline"] = ("multi-device handle: every shard's pass enqueued before the first wait "
                                           "(shards scan concurrently), partial lists merged on the first device")
-            line["sync"] = syncleg
+            if syncleg:
+                line["sync"] = syncleg
         elif pipelined:
             line["config"]["pipeline"] = ("async: 2 batches in flight on the handle's stream "
                                           "(lance_hip_search_batch_device_async / lance_hip_search_wait)"
                                           + ("; batch i-1's all-gather + merge overlap batch i's scan" if world > 1 else ""))
-            line["sync"] = syncleg
+            if syncleg:
+                line["sync"] = syncleg
         if hostb:
             line["host_batch"] = hostb
             # SURVEY.md §8(d)'s QPS: the C-ABI search_batch wall time WITH the H2D of the

@@ -26,8 +26,9 @@ def test_bench_exchange_rehearsal_keeps_exact_ids(exchange):
     env = dict(os.environ)
     for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
+    # --full: the recall / exact-id check against the oracle is not part of a plain run
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "300000", "--steps", "6", "--warmup", "2",
-                        "--settle-s", "0", "--no-cpu-baseline", "--no-host-batch", "--recall-queries", "64",
+                        "--full", "--settle-s", "0", "--no-cpu-baseline", "--no-host-batch", "--recall-queries", "64",
                         "--exchange-rehearsal", "--exchange", exchange],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -12,13 +12,13 @@ B="--no-cpu-baseline --no-host-batch"
 for r in 1 2; do
 	for lib in rel $V; do
 		if [ $lib = rel ]; then unset LANCE_HIP_LIB; else export LANCE_HIP_LIB=$VL; fi
-		step ${T}_${lib}_c2_$r 300 python -u bench.py --steps 20 $B
-		step ${T}_${lib}_rank_$r 300 python -u bench.py --n 125000 --steps 30 $B
-		step ${T}_${lib}_nrank_$r 300 python -u bench.py --n 1250000 --steps 30 $B
+		step ${T}_${lib}_c2_$r 300 python -u bench.py --full --steps 20 $B
+		step ${T}_${lib}_rank_$r 300 python -u bench.py --full --n 125000 --steps 30 $B
+		step ${T}_${lib}_nrank_$r 300 python -u bench.py --full --n 1250000 --steps 30 $B
 	done
 done
 unset LANCE_HIP_LIB
-for f in gpurun_out/${T}_*_[0-9].log; do grep -h '^{' $f | python3 -c "
+for f in $OUT/${T}_*_[0-9].log; do grep -h '^{' $f | python3 -c "
 import json,sys
 for l in sys.stdin:
     d=json.loads(l); print('$(basename $f .log)', d['value'], d['ms_per_step'], d.get('exact_ids_on_recall_subset'))"; done

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Copies a closing run's evidence from gpurun_out/ into profiles/ (tracked):
+"""Copies a closing run's evidence from the run folder ($OUT, default bench_out/) into profiles/ (tracked):
 the bench JSON lines, rocprofv3 kernel stats, the scan kernel's PMC traffic
 (tools/pmc_traffic.py: FETCH_SIZE x2 per MI355X_MICROARCH.md 'HBM') and a
 summary of its SQ / TCC / LDS counters with the derived rates.
@@ -16,7 +16,7 @@ import sys
 from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.path.join(ROOT, os.environ.get("OUT", "bench_out"))
 P = os.path.join(ROOT, "profiles")
 
 

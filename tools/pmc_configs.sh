@@ -1,16 +1,16 @@
 #!/bin/bash
 # PMC traffic passes (MI355X_MICROARCH.md 'HBM': one counter per rocprofv3 run, no trace
 # domains): FETCH_SIZE / WRITE_SIZE of the dominant kernel of each listed config.
-# usage: tools/pmc_configs.sh TAG CONFIG... (configs: c2 nstar c3 c4 c5); summaries -> gpurun_out/TAG_<cfg>_*_traffic.json
+# usage: tools/pmc_configs.sh TAG CONFIG... (configs: c2 nstar c3 c4 c5); summaries -> $OUT/TAG_<cfg>_*_traffic.json
 set -o pipefail
 export TMPDIR=/tmp
-O=gpurun_out
+O=${OUT:-bench_out}
 mkdir -p $O
 T=$1
 shift
 run() { # cfg counter
 	local cfg=$1 ctr=$2
-	timeout -s KILL 300 rocprofv3 --pmc $ctr --output-format csv -d $O/pmc5_${T}_${cfg}_${ctr} -o run -- python3 bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-recall --no-host-batch --sync > $O/pmc5_${T}_${cfg}_${ctr}.log 2>&1 || { echo "pmc $cfg $ctr FAILED"; tail -5 $O/pmc5_${T}_${cfg}_${ctr}.log; exit 1; }
+	timeout -s KILL 300 rocprofv3 --pmc $ctr --output-format csv -d $O/pmc5_${T}_${cfg}_${ctr} -o run -- python3 bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-recall --no-host-batch --sync > $O/pmc5_${T}_${cfg}_${ctr}.log 2>&1 || { echo "pmc $cfg $ctr FAILED"; tail -5 $O/pmc5_${T}_${cfg}_${ctr}.log; exit 1; }
 	echo "pmc $cfg $ctr ok"
 }
 S8="scan8_kernel<12, 4, 2, 0, 0>"

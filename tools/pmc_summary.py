@@ -24,7 +24,7 @@ def main():
     ap.add_argument("kernel")
     ap.add_argument("out")
     ap.add_argument("--simds", type=int, default=1024)
-    ap.add_argument("--dir", default="gpurun_out")
+    ap.add_argument("--dir", default=os.environ.get("OUT", "bench_out"))
     ap.add_argument("--meta", nargs="*", default=[])
     ap.add_argument("--kernel-ms", type=float, default=None, help="average launch time (bench HIP events)")
     ap.add_argument("--xcds", type=int, default=8)
