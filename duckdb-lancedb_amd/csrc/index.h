@@ -276,15 +276,71 @@ struct Index {
 	std::unique_ptr<MetaStore> meta;
 	bool filter_on = false;
 	int64_t filter_live = 0;
-	DevBuf<uint8_t> fmask;
-	DevBuf<float4> faux;
 	int64_t live_rows() const { return filter_on ? filter_live : n_live; }
+	// Filter cache (DESIGN.md "Filtered search"): evaluated predicates as device
+	// bitmasks (bit s of word s / 64 = slot s selected and live), keyed by the
+	// exact predicate bytes, most recently used first.  An entry is valid only at
+	// the (mut_ver, meta version) it was computed at; a stale one is dropped at
+	// lookup, never patched.
+	struct FilterEntry {
+		std::string pred;
+		DevBuf<uint64_t> bits;
+		int64_t count = 0;
+		bool on_device = false;  // evaluated by filter_eval_kernel (else eval_predicate on the host)
+		uint64_t mut_ver = 0, meta_ver = 0;
+		uint64_t id = 0;         // unique per evaluation: what the masked copies are tagged with
+	};
+	std::vector<std::shared_ptr<FilterEntry>> fcache;
+	std::shared_ptr<FilterEntry> fcur;  // the filter of the search in progress
+	int filter_cache_cap = 8;           // option "filter_cache"; 0: every call evaluates
+	bool filter_eval_host = false;      // option "filter_eval" = "host"
+	uint64_t next_filter_id = 1;
+	// [hits, misses, device evaluations, host evaluations, entries resident,
+	//  selected rows of the last filter used, masked-copy launches]
+	int64_t fstat[7] = {0, 0, 0, 0, 0, 0, 0};
+	// one masked copy of each row-term array (rowaux or rowaux_l2, and rowaux8),
+	// tagged with the entry and source it holds: a repeated predicate skips the
+	// copy kernel too
+	DevBuf<float4> faux, faux8;
+	uint64_t faux_id = 0, faux8_id = 0;
+	const float4 *faux_src = nullptr, *faux8_src = nullptr;
+	// device mirror of the metadata columns a program references (8-byte values +
+	// validity byte per slot), per column at the meta version it was uploaded at;
+	// the host `live` bytes per mut_ver; the program of the evaluation in flight
+	struct ColMirror {
+		DevBuf<uint64_t> vals;
+		DevBuf<uint8_t> valid;
+		uint64_t ver = 0;
+	};
+	std::vector<std::unique_ptr<ColMirror>> mirror;
+	DevBuf<uint8_t> dlive, fprog;
+	uint64_t dlive_ver = 0;
+	DevBuf<unsigned long long> fcount;
+	// what a cached filter's meta_ver is compared with: the metadata's version and
+	// the count of IVF models installed (create_index: rows and tombstones are the
+	// same, mut_ver stays, but the entry is dropped as for any other change)
+	uint64_t filter_epoch = 0;
+	uint64_t meta_version() const { return (meta ? meta->version : 0) + (filter_epoch << 40); }
+	void forget_masked_copies() { faux_id = faux8_id = 0; }
+	const float4 *masked_copy(const float4 *base, DevBuf<float4> &buf, uint64_t &id, const float4 *&src) {
+		if (id != fcur->id || src != base || buf.n < (size_t)cap) {
+			buf.need((size_t)cap);
+			launch_mask_rowaux(base, fcur->bits.p, n_slots, cap, buf.p, stream);
+			id = fcur->id;
+			src = base;
+			++fstat[6];
+		}
+		return buf.p;
+	}
 	// the row aux a search reads: `base`, or its filtered copy
-	const float4 *search_aux(const float4 *base) {
-		if (!filter_on) return base;
-		faux.need((size_t)cap);
-		launch_filter_rowaux(base, fmask.p, n_slots, cap, faux.p, stream);
-		return faux.p;
+	const float4 *search_aux(const float4 *base) { return filter_on ? masked_copy(base, faux, faux_id, faux_src) : base; }
+	// the int8 scan's row terms (after ensure_i8)
+	const float4 *search_aux8() { return filter_on ? masked_copy(rowaux8, faux8, faux8_id, faux8_src) : rowaux8; }
+	// evaluates `predicate` through the cache and turns filtering on (FilterScope)
+	void filter_begin(const char *predicate);
+	void filter_end() {
+		filter_on = false;
+		fcur.reset();
 	}
 	int ivf_type_opt = 1;  // 0 IVF_FLAT, 1 IVF_PQ
 	int kmeans_iters = 50;  // lance k-means max_iters default
@@ -494,10 +550,12 @@ struct Index {
 	}
 
 	// the int8 scan applies: an f32 or bf16 store whose rows fit the int8 stages
-	// (ld a multiple of 128, exact integer dot products up to ld = 1024), no
-	// filter, ranking by the index metric
+	// (ld a multiple of 128, exact integer dot products up to ld = 1024),
+	// ranking by the index metric.  With or without a predicate: a filtered
+	// search streams the same int8 rows with the masked copy of rowaux8
+	// (search_aux8), an unselected row reading as a tombstone
 	bool i8_usable() const {
-		return scan_i8 && X && n_slots > 0 && ld % 128 == 0 && ld <= 1024 && !filter_on &&
+		return scan_i8 && X && n_slots > 0 && ld % 128 == 0 && ld <= 1024 &&
 		       !(metric_quirk && metric != METRIC_L2);
 	}
 	// whether a flat search of nq queries for k streams the int8 copy: any k on
@@ -867,8 +925,9 @@ Index *shard_for_add(Index *ix);
 int64_t shard_live(const Index *ix);
 int64_t shard_add(Index *ix, const float *v, int64_t num, int vdev, Index **into, Index *force = nullptr);
 std::vector<int64_t> shard_remove(Index *ix, const int64_t *labels, int64_t n);
+// (odev: device of device-resident outputs; -2 = the handle's first device)
 void shard_search(Index *ix, const float *Q, int qdev, int nq, int k, int nprobes, int refine, const char *pred,
-                  int64_t *L, float *D, int *C, bool out_host);
+                  int64_t *L, float *D, int *C, bool out_host, int odev = -2);
 // asynchronous sharded search (no predicate): every shard's pass enqueued, a
 // ticket back; shard_finish_oldest completes the oldest (certificates on every
 // shard, peer copies, the merge on the first device into the outputs on device
@@ -882,22 +941,17 @@ void shard_compact(Index *ix);
 void shard_create_index(Index *ix, int type, int num_partitions, int num_sub_vectors);
 void shard_counts(Index *ix);
 
-// A search with a predicate: evaluates it over the slots (host, vectorised),
-// uploads the mask and turns filtering on for the scope of the search call.
+// A search with a predicate: the predicate's filter from the handle's cache
+// (evaluated on a miss: on the device when the predicate compiles to a program,
+// else by the host evaluator) and filtering on for the scope of the search
+// call.  A hit does no host pass over the slots, no mask-sized copy and no
+// stream wait.
 struct FilterScope {
 	Index *ix;
 	FilterScope(Index *i, const char *predicate) : ix(i) {
-		if (!predicate || !predicate[0]) return;
-		std::vector<uint8_t> mask;
-		ix->filter_live = eval_predicate(predicate, ix->meta.get(), ix->slot_label, ix->live, mask);
-		ix->bind();
-		ix->fmask.need(std::max<size_t>(mask.size(), 1));
-		if (!mask.empty())
-			HIPCHK(hipMemcpyAsync(ix->fmask.p, mask.data(), mask.size(), hipMemcpyHostToDevice, ix->stream));
-		HIPCHK(hipStreamSynchronize(ix->stream));
-		ix->filter_on = true;
+		if (predicate && predicate[0]) ix->filter_begin(predicate);
 	}
-	~FilterScope() { ix->filter_on = false; }
+	~FilterScope() { ix->filter_end(); }
 };
 
 }  // namespace lhip

@@ -248,6 +248,7 @@ static void install_model(Index *ix, int type, int nlist, int m, const float *dC
 	s->coarse = co.release();
 	ivf_free(ix->ivf);
 	ix->ivf = s.release();
+	++ix->filter_epoch;  // (cached filters serve one table state: a new index is a new state)
 	index_tail(ix);
 }
 

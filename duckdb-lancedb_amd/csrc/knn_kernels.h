@@ -96,10 +96,17 @@ void launch_fill_rowaux(float4 *rowaux, int64_t from, int64_t to, hipStream_t st
 
 // Marks the listed slots dead (rowaux.x = +inf).
 void launch_tombstone(float4 *rowaux, const int64_t *slots, int n, hipStream_t st);
-// dst = src with alpha = +inf on slots [0, n_slots) whose mask byte is 0
-// (filtered search); rows [0, cap) copied
-void launch_filter_rowaux(const float4 *src, const uint8_t *mask, int64_t n_slots, int64_t cap, float4 *dst,
-                          hipStream_t st);
+// ---- filtered search ------------------------------------------------------------
+// dst = src with alpha = +inf on slots [0, n_slots) whose bit of `bits` (slot s:
+// word s / 64, bit s % 64) is clear; rows [0, cap) copied (cap a multiple of
+// SCAN_BR)
+void launch_mask_rowaux(const float4 *src, const uint64_t *bits, int64_t n_slots, int64_t cap, float4 *dst,
+                        hipStream_t st);
+// The predicate program (filter_program.h: n_code FpInstr at `code`, its literal
+// table, its FpCol column table; all device memory) over slots [0, n_slots):
+// bits[(n_slots + 63) / 64] = live && TRUE per slot, *count += the selected rows.
+void launch_filter_eval(const void *code, int n_code, const uint64_t *lits, const void *cols, const uint8_t *live,
+                        int64_t n_slots, uint64_t *bits, unsigned long long *count, hipStream_t st);
 
 // ---- search ------------------------------------------------------------------
 // int8 scan (scan_i8): int8 queries (one scale for the batch) into Qb's rows

@@ -314,20 +314,23 @@ void launch_tombstone(float4 *rowaux, const int64_t *slots, int n, hipStream_t s
 	tombstone_kernel<<<dim3((n + 255) / 256), dim3(256), 0, st>>>(rowaux, slots, n);
 }
 
-__global__ void filter_rowaux_kernel(const float *__restrict__ src, const uint8_t *__restrict__ mask, int64_t n_slots,
-                                     int64_t cap, float *__restrict__ dst) {
+// The masked copy of the row terms a filtered search reads (with the other
+// row-term kernels; the filter itself comes from filter_kernels.hip).
+__global__ void mask_rowaux_kernel(const float *__restrict__ src, const unsigned long long *__restrict__ bits,
+                                   int64_t n_slots, int64_t cap, float *__restrict__ dst) {
 	const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r >= cap) return;
 #pragma unroll
 	for (int c = 0; c < 4; ++c) dst[raix(r, c)] = src[raix(r, c)];
-	if (r < n_slots && !mask[r]) dst[raix(r, 0)] = F_INF;
+	if (r < n_slots && !((bits[r >> 6] >> (r & 63)) & 1ull)) dst[raix(r, 0)] = F_INF;
 }
 
-void launch_filter_rowaux(const float4 *src, const uint8_t *mask, int64_t n_slots, int64_t cap, float4 *dst,
-                          hipStream_t st) {
+void launch_mask_rowaux(const float4 *src, const uint64_t *bits, int64_t n_slots, int64_t cap, float4 *dst,
+                        hipStream_t st) {
 	if (cap <= 0) return;
-	filter_rowaux_kernel<<<dim3((unsigned)((cap + 255) / 256)), 256, 0, st>>>(
-	    reinterpret_cast<const float *>(src), mask, n_slots, cap, reinterpret_cast<float *>(dst));
+	mask_rowaux_kernel<<<dim3((unsigned)((cap + 255) / 256)), 256, 0, st>>>(
+	    reinterpret_cast<const float *>(src), reinterpret_cast<const unsigned long long *>(bits), n_slots, cap,
+	    reinterpret_cast<float *>(dst));
 }
 
 // ---------------------------------------------------------------------------

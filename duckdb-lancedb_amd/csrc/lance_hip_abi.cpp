@@ -34,6 +34,107 @@
 
 namespace lhip {
 
+// The filter of `predicate` for the search in progress: the cached entry when it
+// was computed at the current (mut_ver, meta version), else a new evaluation.
+// Liveness comes from the host `live` bytes, uploaded once per mut_ver (exactly
+// what the host evaluator ANDs with; the row terms' +inf code could also mark a
+// live row whose norm overflows).
+void Index::filter_begin(const char *predicate) {
+	bind();
+	const std::string pred(predicate);
+	const uint64_t mv = meta_version();
+	std::shared_ptr<FilterEntry> e;
+	for (size_t i = 0; i < fcache.size(); ++i) {
+		if (fcache[i]->pred != pred) continue;
+		if (fcache[i]->mut_ver == mut_ver && fcache[i]->meta_ver == mv) e = fcache[i];
+		fcache.erase(fcache.begin() + (long)i);
+		break;
+	}
+	if (e) {
+		++fstat[0];
+	} else {
+		++fstat[1];
+		e = std::make_shared<FilterEntry>();
+		e->pred = pred;
+		e->mut_ver = mut_ver;
+		e->meta_ver = mv;
+		e->id = next_filter_id++;
+		const int64_t n_words = (n_slots + 63) / 64;
+		e->bits.need((size_t)std::max<int64_t>(n_words, 1));
+		FilterProgram pg;
+		std::string why;
+		bool dev = !filter_eval_host && compile_predicate(pred, meta.get(), pg, why);
+		if (dev)
+			for (int ci : pg.cols)  // (a column shorter than the store: the host evaluator's business)
+				if (ci >= 0 && meta->cols[(size_t)ci].size() != (size_t)n_slots) dev = false;
+		if (dev && n_slots > 0) {
+			// column mirrors and liveness, refreshed when their version moved
+			if (mirror.size() < (meta ? meta->cols.size() : 0)) mirror.resize(meta->cols.size());
+			std::vector<FpCol> cols;
+			for (int ci : pg.cols) {
+				if (ci < 0) {
+					cols.push_back(FpCol{dlabels, nullptr});
+					continue;
+				}
+				if (!mirror[(size_t)ci]) mirror[(size_t)ci].reset(new ColMirror());
+				ColMirror &m = *mirror[(size_t)ci];
+				const MetaColumn &c = meta->cols[(size_t)ci];
+				if (m.ver != mv || m.vals.n < (size_t)n_slots) {
+					m.vals.need((size_t)n_slots);
+					m.valid.need((size_t)n_slots);
+					const void *src = c.type == COL_FLOAT ? static_cast<const void *>(c.f.data()) : c.i.data();
+					HIPCHK(hipMemcpyAsync(m.vals.p, src, (size_t)n_slots * 8, hipMemcpyHostToDevice, stream));
+					HIPCHK(hipMemcpyAsync(m.valid.p, c.valid.data(), (size_t)n_slots, hipMemcpyHostToDevice, stream));
+					m.ver = mv;
+				}
+				cols.push_back(FpCol{m.vals.p, m.valid.p});
+			}
+			if (dlive_ver != mut_ver || dlive.n < (size_t)n_slots) {
+				dlive.need((size_t)n_slots);
+				HIPCHK(hipMemcpyAsync(dlive.p, live.data(), (size_t)n_slots, hipMemcpyHostToDevice, stream));
+				dlive_ver = mut_ver;
+			}
+			// the program in one small device buffer: [literals | columns | instructions]
+			const size_t lb = pg.lits.size() * 8, cb = cols.size() * sizeof(FpCol), ib = pg.code.size() * sizeof(FpInstr);
+			std::vector<uint8_t> blob(lb + cb + ib);
+			if (lb) memcpy(blob.data(), pg.lits.data(), lb);
+			if (cb) memcpy(blob.data() + lb, cols.data(), cb);
+			memcpy(blob.data() + lb + cb, pg.code.data(), ib);
+			fprog.need(blob.size());
+			fcount.need(1);
+			HIPCHK(hipMemcpyAsync(fprog.p, blob.data(), blob.size(), hipMemcpyHostToDevice, stream));
+			HIPCHK(hipMemsetAsync(fcount.p, 0, sizeof(unsigned long long), stream));
+			launch_filter_eval(fprog.p + lb + cb, (int)pg.code.size(), reinterpret_cast<const uint64_t *>(fprog.p),
+			                   fprog.p + lb, dlive.p, n_slots, e->bits.p, fcount.p, stream);
+			HIPCHK(hipGetLastError());
+			unsigned long long cnt = 0;
+			HIPCHK(hipMemcpyAsync(&cnt, fcount.p, sizeof(cnt), hipMemcpyDeviceToHost, stream));
+			HIPCHK(hipStreamSynchronize(stream));
+			e->count = (int64_t)cnt;
+			e->on_device = true;
+			++fstat[2];
+		} else {
+			std::vector<uint8_t> mask;
+			e->count = eval_predicate(pred, meta.get(), slot_label, live, mask);
+			std::vector<uint64_t> words((size_t)std::max<int64_t>(n_words, 1), 0);
+			for (size_t s = 0; s < mask.size(); ++s)
+				if (mask[s]) words[s >> 6] |= 1ull << (s & 63);
+			HIPCHK(hipMemcpyAsync(e->bits.p, words.data(), words.size() * 8, hipMemcpyHostToDevice, stream));
+			HIPCHK(hipStreamSynchronize(stream));
+			++fstat[3];
+		}
+	}
+	if (filter_cache_cap > 0) {
+		fcache.insert(fcache.begin(), e);
+		while ((int)fcache.size() > filter_cache_cap) fcache.pop_back();
+	}
+	fstat[4] = (int64_t)fcache.size();
+	fstat[5] = e->count;
+	fcur = e;
+	filter_live = e->count;
+	filter_on = true;
+}
+
 void Index::search_device(const float *dQ, int nq, int k, int refine, int64_t *dL, float *dD, int *dC) {
 	for (auto &v : last_stats) v = 0;
 	// one pipeline pass covers up to MAX_PASS_Q queries (several query tiles
@@ -109,7 +210,7 @@ bool Index::enqueue_chunk(const float *dQ, int nq, int k, int refine, int64_t *d
 	if (use8) {
 		ensure_i8();
 		sv.Xscan = Xq;
-		sv.scan_aux = rowaux8;
+		sv.scan_aux = search_aux8();  // (filtered search: the masked copy of the int8 row terms)
 		sv.scan_i8 = 1;
 		sv.tstat = tstat8;
 	}
@@ -969,6 +1070,35 @@ int64_t lance_hip_predicate_mask(void *arrow_schema, void *arrow_array, const in
 	API_GUARD("predicate failed: ", -1)
 }
 
+// NEW — lance_hip_predicate_mask through the predicate program: the predicate
+// compiled (meta.cpp compile_predicate) and the per-row interpreter the device
+// evaluator runs (filter_program.h) in a host loop.  No device.  -1 with a
+// message beginning "predicate: not device-evaluable" when the predicate does
+// not compile to a program.
+int64_t lance_hip_predicate_mask_program(void *arrow_schema, void *arrow_array, const int64_t *labels,
+                                         const uint8_t *live, const char *predicate, uint8_t *out_mask, char *err_buf,
+                                         int err_buf_len) {
+	try {
+		if (!arrow_schema || !arrow_array || !labels || !live || !out_mask) throw Error("null argument");
+		const ArrowSchema *sch = static_cast<const ArrowSchema *>(arrow_schema);
+		auto m = lhip::MetaStore::from_schema(sch);
+		std::vector<float> vecs;
+		const int64_t n = m->import_batch(sch, static_cast<const ArrowArray *>(arrow_array), vecs);
+		lhip::FilterProgram pg;
+		std::string why;
+		if (!lhip::compile_predicate(cstr(predicate), m.get(), pg, why)) {
+			lhip::write_err(err_buf, err_buf_len, "predicate: not device-evaluable (" + why + ")");
+			return -1;
+		}
+		std::vector<int64_t> lab(labels, labels + n);
+		std::vector<uint8_t> lv(live, live + n), mask;
+		const int64_t c = lhip::run_program_host(pg, m.get(), lab, lv, mask);
+		if (n > 0) memcpy(out_mask, mask.data(), (size_t)n);
+		return c;
+	}
+	API_GUARD("predicate failed: ", -1)
+}
+
 // The call the reference's C++ already makes (lance_index.cpp:481-486) with no
 // declaration or Rust export behind it: a scalar index on a
 // metadata column, used by search predicates that compare the column with a
@@ -1357,6 +1487,21 @@ int32_t lance_detached_get_all_vectors(void *handle, int64_t *out_labels, float 
 // the options of one store (a single-device handle, or each shard of a
 // multi-device one); throws on a bad key / value
 static void set_option_store(Index *ix, const std::string &k, const std::string &v) {
+	// (an option may rebuild a row-term array in place: scan_i8, metric_quirk)
+	ix->forget_masked_copies();
+	if (k == "filter_eval") {  // "auto": predicate programs on the device where they compile; "host": always eval_predicate
+		if (v != "auto" && v != "host") throw Error("filter_eval must be 'auto' or 'host'");
+		ix->filter_eval_host = v == "host";
+		return;
+	}
+	if (k == "filter_cache") {  // evaluated filters kept per handle (LRU); 0: every call evaluates
+		const int c = std::stoi(v);
+		if (c < 0 || c > 1024) throw Error("filter_cache must be in [0, 1024]");
+		ix->filter_cache_cap = c;
+		while ((int)ix->fcache.size() > c) ix->fcache.pop_back();
+		ix->fstat[4] = (int64_t)ix->fcache.size();
+		return;
+	}
 	if (k == "s8_couple") {  // scan8 pair coupling lag in 32-row units (0 = off; results exact for any value)
 		const int c = std::stoi(v);
 		if (c < 0 || c > 4096) throw Error("s8_couple must be in [0, 4096]");
@@ -1694,6 +1839,115 @@ int32_t lance_hip_search_batch_device(void *handle, const float *d_queries, int3
 		return nq;
 	}
 	API_GUARD("search failed: ", -1)
+}
+
+// lance_hip_search_batch_device with a predicate (NULL / "": exactly that
+// call).  Synchronous, the prefilter semantics of lance_detached_search_batch:
+// with no selected row every count is 0, labels -1 and distances NaN.
+int32_t lance_hip_search_batch_device_filtered(void *handle, const float *d_queries, int32_t nq, int32_t dim,
+                                               int32_t k, int32_t nprobes, int32_t refine_factor,
+                                               const char *predicate, int64_t *d_out_labels, float *d_out_distances,
+                                               int32_t *d_out_counts, char *err_buf, int err_buf_len) {
+	if (!predicate || !predicate[0])
+		return lance_hip_search_batch_device(handle, d_queries, nq, dim, k, nprobes, refine_factor, d_out_labels,
+		                                     d_out_distances, d_out_counts, err_buf, err_buf_len);
+	if (!handle) {
+		lhip::write_err(err_buf, err_buf_len, "null handle");
+		return -1;
+	}
+	try {
+		Index *ix = as_index(handle);
+		if (dim != ix->dim)
+			throw Error("expected query dimension " + std::to_string(ix->dim) + ", got " + std::to_string(dim));
+		if (k <= 0) throw Error("k must be positive");
+		if (nq < 0) throw Error("negative query count");
+		if (nq == 0) return 0;
+		if (!d_queries || !d_out_labels || !d_out_distances || !d_out_counts) throw Error("null buffer");
+		std::lock_guard<std::mutex> g(ix->mu);
+		ix->bind();
+		if (ix->sharded()) {
+			lhip::shard_search(ix, d_queries, pointer_device(d_queries), nq, k, nprobes, refine_factor, predicate,
+			                   d_out_labels, d_out_distances, d_out_counts, false, pointer_device(d_out_labels));
+			return nq;
+		}
+		lhip::FilterScope fs(ix, predicate);
+		if (ix->live_rows() == 0) {
+			// (all-ones bytes: label -1, a NaN distance)
+			HIPCHK(hipMemsetAsync(d_out_counts, 0, (size_t)nq * sizeof(int32_t), ix->stream));
+			HIPCHK(hipMemsetAsync(d_out_labels, 0xFF, (size_t)nq * k * sizeof(int64_t), ix->stream));
+			HIPCHK(hipMemsetAsync(d_out_distances, 0xFF, (size_t)nq * k * sizeof(float), ix->stream));
+			HIPCHK(hipStreamSynchronize(ix->stream));
+			return nq;
+		}
+		ix->search_any(d_queries, nq, k, nprobes, refine_factor, d_out_labels, d_out_distances, d_out_counts);
+		return nq;
+	}
+	API_GUARD("search failed: ", -1)
+}
+
+// Evaluates the predicate's filter now and caches it; the selected row count.
+int64_t lance_hip_filter_prepare(void *handle, const char *predicate, char *err_buf, int err_buf_len) {
+	if (!handle) {
+		lhip::write_err(err_buf, err_buf_len, "null handle");
+		return -1;
+	}
+	try {
+		Index *ix = as_index(handle);
+		if (!predicate || !predicate[0]) throw Error("empty predicate");
+		std::lock_guard<std::mutex> g(ix->mu);
+		ix->bind();
+		int64_t total = 0;
+		if (ix->sharded()) {
+			for (auto &sh : ix->shards) {
+				lhip::FilterScope fs(sh.get(), predicate);
+				total += sh->filter_live;
+			}
+			return total;
+		}
+		lhip::FilterScope fs(ix, predicate);
+		return ix->filter_live;
+	}
+	API_GUARD("filter_prepare failed: ", -1)
+}
+
+// The cached filter of the predicate as one byte per slot (storage order =
+// ascending label order, deleted rows included: 0); the slot count.
+int64_t lance_hip_filter_mask(void *handle, const char *predicate, uint8_t *out_mask, int64_t capacity, char *err_buf,
+                              int err_buf_len) {
+	if (!handle) {
+		lhip::write_err(err_buf, err_buf_len, "null handle");
+		return -1;
+	}
+	try {
+		Index *ix = as_index(handle);
+		if (!predicate || !predicate[0]) throw Error("empty predicate");
+		std::lock_guard<std::mutex> g(ix->mu);
+		if (ix->sharded()) throw Error("filter_mask is not supported on a multi-device handle");
+		if (capacity < ix->n_slots || (!out_mask && ix->n_slots > 0)) throw Error("output buffer too small");
+		lhip::FilterScope fs(ix, predicate);
+		const int64_t n = ix->n_slots;
+		std::vector<uint64_t> words((size_t)(n + 63) / 64);
+		if (n > 0) {
+			HIPCHK(hipMemcpyAsync(words.data(), ix->fcur->bits.p, words.size() * 8, hipMemcpyDeviceToHost, ix->stream));
+			HIPCHK(hipStreamSynchronize(ix->stream));
+		}
+		for (int64_t s = 0; s < n; ++s) out_mask[s] = (uint8_t)((words[(size_t)(s >> 6)] >> (s & 63)) & 1);
+		return n;
+	}
+	API_GUARD("filter_mask failed: ", -1)
+}
+
+// Filter cache counters of the handle (of the first store of a multi-device
+// handle): out[0] hits, [1] misses, [2] filters evaluated on the device, [3] on
+// the host, [4] entries resident, [5] selected rows of the last filter used,
+// [6] masked-copy kernel launches.
+int32_t lance_hip_filter_info(void *handle, int64_t *out, int32_t n) {
+	if (!handle || !out) return -1;
+	Index *ix = as_index(handle);
+	std::lock_guard<std::mutex> g(ix->mu);
+	const Index *s = ix->sharded() ? ix->shards[0].get() : ix;
+	for (int32_t i = 0; i < n && i < 7; ++i) out[i] = s->fstat[i];
+	return 0;
 }
 
 int64_t lance_hip_search_batch_device_async(void *handle, const float *d_queries, int32_t nq, int32_t dim, int32_t k,

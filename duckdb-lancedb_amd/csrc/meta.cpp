@@ -69,6 +69,7 @@ int64_t MetaStore::import_batch(const ArrowSchema *schema, const ArrowArray *arr
 		            std::to_string(cols.size() + 1));
 	const int64_t n = array->length, off0 = array->offset;
 	int ci = 0;
+	++version;
 	for (int64_t c = 0; c < schema->n_children; ++c) {
 		const ArrowSchema *cs = schema->children[c];
 		const ArrowArray *ca = array->children[c];
@@ -154,6 +155,7 @@ int64_t MetaStore::import_batch(const ArrowSchema *schema, const ArrowArray *arr
 }
 
 void MetaStore::keep_slots(const std::vector<int64_t> &keep) {
+	++version;
 	for (auto &c : cols) {
 		MetaColumn nc;
 		nc.valid.reserve(keep.size());
@@ -206,6 +208,7 @@ void MetaColumn::build_index(const std::string &ty) {
 
 void MetaStore::append_rows(const MetaStore &src, const std::vector<int64_t> &src_slots) {
 	if (src.cols.size() != cols.size()) throw Error("merged indexes have different metadata columns");
+	++version;
 	for (size_t c = 0; c < cols.size(); ++c) {
 		MetaColumn &d = cols[c];
 		const MetaColumn &s = src.cols[c];
@@ -220,6 +223,7 @@ void MetaStore::append_rows(const MetaStore &src, const std::vector<int64_t> &sr
 }
 
 void MetaStore::truncate(size_t n) {
+	++version;
 	for (auto &c : cols) {
 		c.valid.resize(std::min(n, c.valid.size()));
 		if (c.type == COL_INT || c.type == COL_BOOL) c.i.resize(c.valid.size());
@@ -229,6 +233,7 @@ void MetaStore::truncate(size_t n) {
 }
 
 void MetaStore::append_nulls(int64_t n) {
+	++version;
 	for (auto &c : cols) {
 		c.valid.insert(c.valid.end(), (size_t)n, 0);
 		if (c.type == COL_INT || c.type == COL_BOOL) c.i.insert(c.i.end(), (size_t)n, 0);
@@ -315,6 +320,7 @@ void MetaStore::serialize_rows(int64_t s0, int64_t n, std::vector<uint8_t> &out)
 void MetaStore::deserialize_rows(const uint8_t *p, size_t len) {
 	Reader r{p, p + len};
 	const int64_t n = r.v<int64_t>();
+	++version;
 	for (auto &c : cols) {
 		const size_t b = c.valid.size();
 		c.valid.resize(b + (size_t)n);
@@ -857,7 +863,257 @@ struct Eval {
 	}
 };
 
+// The AST as a postfix program (filter_program.h).  Mirrors Eval::run case by
+// case and in its order; whatever Eval could throw on, or this cannot prove it
+// reproduces, clears `ok` (the predicate then goes to Eval whole).
+struct Compiler {
+	const MetaStore *meta;
+	FilterProgram &pg;
+	bool ok = true;
+	std::string why;
+	std::string unknown;  // first unknown column, in Eval's order
+	int depth = 0, max_depth = 0;
+
+	void fail(const std::string &w) {
+		if (ok) why = w;
+		ok = false;
+	}
+	// Eval::column's lookup: -2 unknown, -1 label, else the column's position
+	int find(const std::string &name) const {
+		if (meta)
+			for (size_t i = 0; i < meta->cols.size(); ++i)
+				if (meta->cols[i].name == name) return (int)i;
+		if (name == "label") return -1;
+		if (meta)
+			for (size_t i = 0; i < meta->cols.size(); ++i)
+				if (upper(meta->cols[i].name) == upper(name)) return (int)i;
+		return -2;
+	}
+	// the program's reference of a column (-1 when unusable) and its type
+	int colref(const std::string &name, ColType &type) {
+		const int ci = find(name);
+		type = COL_INT;
+		if (ci == -2) {
+			if (unknown.empty()) unknown = "predicate: no column named '" + name + "'";
+			return -1;
+		}
+		if (ci >= 0) type = meta->cols[(size_t)ci].type;
+		if (type == COL_STRING) {
+			fail("string column '" + name + "'");
+			return -1;
+		}
+		for (size_t i = 0; i < pg.cols.size(); ++i)
+			if (pg.cols[i] == ci) return (int)i;
+		if ((int)pg.cols.size() >= FP_MAX_COLS) {
+			fail("more than " + std::to_string(FP_MAX_COLS) + " columns");
+			return -1;
+		}
+		pg.cols.push_back(ci);
+		return (int)pg.cols.size() - 1;
+	}
+	void emit(FpInstr in, int pops) {
+		depth += 1 - pops;
+		max_depth = std::max(max_depth, depth);
+		pg.code.push_back(in);
+	}
+	void push_const(int tri) { emit(FpInstr{FP_CONST, 0, 0, 0, (uint16_t)tri, 0, 0}, 0); }
+	static int cmp_code(const std::string &op) {
+		if (op == "=") return FP_EQ;
+		if (op == "!=") return FP_NE;
+		if (op == "<") return FP_LT;
+		if (op == "<=") return FP_LE;
+		if (op == ">") return FP_GT;
+		return FP_GE;
+	}
+	static uint64_t bits_of(double d) {
+		uint64_t u;
+		memcpy(&u, &d, 8);
+		return u;
+	}
+	int add_lit(uint64_t u) {
+		if ((int)pg.lits.size() >= FP_MAX_LITS) {
+			fail("more than " + std::to_string(FP_MAX_LITS) + " literals");
+			return 0;
+		}
+		pg.lits.push_back(u);
+		return (int)pg.lits.size() - 1;
+	}
+	// a non-NULL literal against a column of `type` as cmp_vals pairs them:
+	// the literal's bits and class, false when cmp_vals would throw
+	bool pair_lit(ColType type, const Value &lit, uint64_t &u, int &cls) {
+		if (lit.kind == Value::STR) return fail("string literal"), false;
+		if (type == COL_BOOL || lit.kind == Value::BOOL) {
+			if (type != COL_BOOL || lit.kind != Value::BOOL) return fail("boolean compared with a non-boolean"), false;
+			u = (uint64_t)lit.i;
+			cls = FP_INT;
+			return true;
+		}
+		if (type == COL_INT && lit.kind == Value::INT) {
+			u = (uint64_t)lit.i;
+			cls = FP_INT;
+		} else {  // doubles: (double) of an integer literal, as cmp_vals converts it
+			u = bits_of(lit.kind == Value::INT ? (double)lit.i : lit.f);
+			cls = FP_FLT;
+		}
+		return true;
+	}
+	static int cls_of(ColType t) { return t == COL_FLOAT ? FP_FLT : FP_INT; }
+
+	void cmp(const Node &a, const Node &b, const std::string &op) {
+		if (a.kind == Node::LIT && b.kind == Node::LIT) {
+			const Value &x = a.lit, &y = b.lit;
+			if (x.kind == Value::NUL || y.kind == Value::NUL) return push_const(T_NULL);
+			if (x.kind == Value::STR || y.kind == Value::STR) return fail("string literal");
+			if ((x.kind == Value::BOOL) != (y.kind == Value::BOOL)) return fail("boolean compared with a non-boolean");
+			const int cx = x.kind == Value::FLT ? FP_FLT : FP_INT, cy = y.kind == Value::FLT ? FP_FLT : FP_INT;
+			const int c = fp_cmp3(cx == FP_FLT ? bits_of(x.f) : (uint64_t)x.i, cx, cy == FP_FLT ? bits_of(y.f) : (uint64_t)y.i, cy);
+			return push_const(fp_test(c, cmp_code(op)) ? T_TRUE : T_FALSE);
+		}
+		if ((a.kind == Node::COL && b.kind == Node::LIT) || (a.kind == Node::LIT && b.kind == Node::COL)) {
+			const bool col_first = a.kind == Node::COL;
+			const Node &cn = col_first ? a : b, &ln = col_first ? b : a;
+			ColType type;
+			const int c = colref(cn.col, type);
+			if (c < 0) return push_const(T_NULL);
+			if (ln.lit.kind == Value::NUL) return push_const(T_NULL);
+			uint64_t u;
+			int cls;
+			if (!pair_lit(type, ln.lit, u, cls)) return;
+			const int l = add_lit(u);
+			const std::string o = col_first ? op : std::string(Eval::flip(op));
+			return emit(FpInstr{FP_CMP_CL, (uint8_t)cmp_code(o), (uint8_t)cls_of(type), (uint8_t)cls, (uint16_t)c, (uint16_t)l, 0}, 0);
+		}
+		if (a.kind == Node::COL && b.kind == Node::COL) {
+			ColType ta, tb;
+			const int ca = colref(a.col, ta), cb = colref(b.col, tb);
+			if (ca < 0 || cb < 0) return push_const(T_NULL);
+			if ((ta == COL_BOOL) != (tb == COL_BOOL)) return fail("boolean compared with a non-boolean");
+			return emit(FpInstr{FP_CMP_CC, (uint8_t)cmp_code(op), (uint8_t)cls_of(ta), (uint8_t)cls_of(tb), (uint16_t)ca, (uint16_t)cb, 0}, 0);
+		}
+		fail("comparison operands must be columns or literals");
+	}
+
+	void in_list(const Node &x) {
+		const Node &a = *x.kids[0];
+		// a column against literals of one class: one instruction over a literal range
+		bool flat = a.kind == Node::COL;
+		for (size_t i = 1; flat && i < x.kids.size(); ++i) flat = x.kids[i]->kind == Node::LIT;
+		if (flat) {
+			ColType type;
+			const int c = colref(a.col, type);
+			if (c < 0) return push_const(T_NULL);
+			std::vector<uint64_t> us;
+			int cls = -1;
+			bool has_null = false, one_class = true;
+			for (size_t i = 1; i < x.kids.size(); ++i) {
+				const Value &l = x.kids[i]->lit;
+				if (l.kind == Value::NUL) {
+					has_null = true;
+					continue;
+				}
+				uint64_t u;
+				int k;
+				if (!pair_lit(type, l, u, k)) return;
+				if (cls >= 0 && k != cls) one_class = false;
+				cls = k;
+				us.push_back(u);
+			}
+			if (one_class) {
+				if (pg.lits.size() + us.size() > (size_t)FP_MAX_LITS) return fail("more than " + std::to_string(FP_MAX_LITS) + " literals");
+				const size_t b = pg.lits.size();
+				if (b > 0xFFFF) return fail("literal table too long");
+				pg.lits.insert(pg.lits.end(), us.begin(), us.end());
+				return emit(FpInstr{FP_IN_CL, (uint8_t)(cls < 0 ? FP_INT : cls), (uint8_t)cls_of(type),
+				                    (uint8_t)((x.neg ? 1 : 0) | (has_null ? 2 : 0)), (uint16_t)c, (uint16_t)b, (uint32_t)us.size()}, 0);
+			}
+		}
+		// Eval's form: FALSE OR (a = l1) OR (a = l2) ..
+		for (size_t i = 1; i < x.kids.size() && ok; ++i) {
+			cmp(a, *x.kids[i], "=");
+			if (i > 1) emit(FpInstr{FP_OR, 0, 0, 0, 0, 0, 0}, 2);
+		}
+		if (x.neg) emit(FpInstr{FP_NOT, 0, 0, 0, 0, 0, 0}, 1);
+	}
+
+	void run(const Node &x) {
+		if (!ok) return;
+		switch (x.kind) {
+		case Node::AND:
+		case Node::OR:
+			run(*x.kids[0]);
+			run(*x.kids[1]);
+			return emit(FpInstr{(uint8_t)(x.kind == Node::AND ? FP_AND : FP_OR), 0, 0, 0, 0, 0, 0}, 2);
+		case Node::NOT:
+			run(*x.kids[0]);
+			return emit(FpInstr{FP_NOT, 0, 0, 0, 0, 0, 0}, 1);
+		case Node::CMP: return cmp(*x.kids[0], *x.kids[1], x.op);
+		case Node::ISNULL: {
+			const Node &a = *x.kids[0];
+			if (a.kind == Node::LIT) return push_const(((a.lit.kind == Value::NUL) != x.neg) ? T_TRUE : T_FALSE);
+			if (a.kind == Node::COL) {
+				ColType type;
+				const int c = colref(a.col, type);
+				if (c < 0) return push_const(T_NULL);
+				return emit(FpInstr{FP_ISNULL_COL, 0, 0, (uint8_t)(x.neg ? 1 : 0), (uint16_t)c, 0, 0}, 0);
+			}
+			run(a);
+			return emit(FpInstr{FP_ISNULL, 0, 0, (uint8_t)(x.neg ? 1 : 0), 0, 0, 0}, 1);
+		}
+		case Node::IN: return in_list(x);
+		case Node::COL: {
+			ColType type;
+			const int c = colref(x.col, type);
+			if (c < 0) return push_const(T_NULL);
+			if (type != COL_BOOL) return fail("column '" + x.col + "' is not boolean");
+			return emit(FpInstr{FP_BOOLCOL, 0, 0, 0, (uint16_t)c, 0, 0}, 0);
+		}
+		case Node::LIT:
+			if (x.lit.kind != Value::BOOL && x.lit.kind != Value::NUL) return fail("not a boolean expression");
+			return push_const(x.lit.kind == Value::NUL ? T_NULL : (x.lit.i ? T_TRUE : T_FALSE));
+		}
+	}
+};
+
 }  // namespace
+
+bool compile_predicate(const std::string &predicate, const MetaStore *meta, FilterProgram &prog, std::string &why) {
+	Parser ps{tokenize(predicate)};
+	NodeP root = ps.expr();
+	if (ps.peek().kind != Tok::END) throw Error("predicate: unexpected '" + ps.peek().text + "'");
+	prog = FilterProgram();
+	Compiler c{meta, prog};
+	c.run(*root);
+	if (c.ok && (int)prog.code.size() > FP_MAX_INSTR) c.fail("more than " + std::to_string(FP_MAX_INSTR) + " instructions");
+	if (c.ok && c.max_depth > FP_MAX_STACK) c.fail("expression deeper than " + std::to_string(FP_MAX_STACK));
+	if (!c.ok) {
+		why = c.why;
+		return false;
+	}
+	if (!c.unknown.empty()) throw Error(c.unknown);
+	return true;
+}
+
+int64_t run_program_host(const FilterProgram &prog, const MetaStore *meta, const std::vector<int64_t> &labels,
+                         const std::vector<uint8_t> &live, std::vector<uint8_t> &mask) {
+	std::vector<FpCol> cols;
+	for (int ci : prog.cols) {
+		if (ci < 0) {
+			cols.push_back(FpCol{labels.data(), nullptr});
+			continue;
+		}
+		const MetaColumn &c = meta->cols[(size_t)ci];
+		if (c.size() < labels.size()) throw Error("predicate: column '" + c.name + "' is shorter than the table");
+		cols.push_back(FpCol{c.type == COL_FLOAT ? static_cast<const void *>(c.f.data()) : c.i.data(), c.valid.data()});
+	}
+	mask.assign(labels.size(), 0);
+	int64_t cnt = 0;
+	for (size_t s = 0; s < labels.size(); ++s)
+		if (live[s] && fp_eval_row(prog.code.data(), (int)prog.code.size(), prog.lits.data(), cols.data(), (int64_t)s)) {
+			mask[s] = 1;
+			++cnt;
+		}
+	return cnt;
+}
 
 int64_t eval_predicate(const std::string &predicate, const MetaStore *meta, const std::vector<int64_t> &labels,
                        const std::vector<uint8_t> &live, std::vector<uint8_t> &mask) {

@@ -25,6 +25,8 @@
 #include <string>
 #include <vector>
 
+#include "filter_program.h"
+
 // Arrow C Data Interface (https://arrow.apache.org/docs/format/CDataInterface.html), the
 // stable C ABI DuckDB's ArrowConverter produces (lance_index.cpp:297-304, :340-354)
 struct ArrowSchema {
@@ -85,6 +87,10 @@ struct MetaStore {
 	int vector_pos = 0;       // its position among the struct's children
 	int dim = 0;
 	std::vector<MetaColumn> cols;
+	// bumped by everything that changes a column's rows (import, append,
+	// truncate, keep_slots, deserialize): device mirrors of the columns and
+	// cached filters are valid at one version only
+	uint64_t version = 1;
 
 	// schema of a create_from_arrow table: "+s" with one "+w:<dim>" float32 child
 	static std::unique_ptr<MetaStore> from_schema(const ArrowSchema *schema);
@@ -110,5 +116,28 @@ struct MetaStore {
 // Throws Error on a syntax error or an unknown column.  Returns the count.
 int64_t eval_predicate(const std::string &predicate, const MetaStore *meta, const std::vector<int64_t> &labels,
                        const std::vector<uint8_t> &live, std::vector<uint8_t> &mask);
+
+// A predicate compiled for the per-row interpreter of filter_program.h.
+// Limits (filter_program.h): at most FP_MAX_INSTR (256) instructions,
+// FP_MAX_LITS (4096) literals, FP_MAX_COLS (16) distinct columns and a value
+// stack of FP_MAX_STACK (64) entries; a predicate past any of them, or one the
+// compiler cannot prove it handles (string columns or literals, a type pairing
+// the host evaluator rejects, a non-boolean operand of AND / OR / NOT), is not
+// device-evaluable and goes to eval_predicate whole, so its result and its
+// errors stay what they are there.
+struct FilterProgram {
+	std::vector<FpInstr> code;
+	std::vector<uint64_t> lits;  // int64 or f64 bits
+	std::vector<int> cols;       // referenced columns: index into MetaStore::cols, -1 = `label`
+};
+// Parses and compiles.  Throws Error on a syntax error, and on an unknown
+// column of an otherwise device-evaluable predicate (the messages of
+// eval_predicate).  Returns false with the reason in `why` when the predicate
+// is not device-evaluable.
+bool compile_predicate(const std::string &predicate, const MetaStore *meta, FilterProgram &prog, std::string &why);
+// The program over host columns, slots [0, labels.size()): the mask and count
+// eval_predicate gives.
+int64_t run_program_host(const FilterProgram &prog, const MetaStore *meta, const std::vector<int64_t> &labels,
+                         const std::vector<uint8_t> &live, std::vector<uint8_t> &mask);
 
 }  // namespace lhip

@@ -305,11 +305,12 @@ void shard_finish_oldest(Index *ix) {
 // Synchronous sharded search (the host-buffer entry points, predicates): the
 // predicate's mask per shard (FilterScope) for the duration of the search.
 void shard_search(Index *ix, const float *Q, int qdev, int nq, int k, int nprobes, int refine, const char *pred,
-                  int64_t *L, float *D, int *C, bool out_host) {
+                  int64_t *L, float *D, int *C, bool out_host, int odev) {
 	ix->drain();
 	std::vector<std::unique_ptr<FilterScope>> fs;
 	for (auto &sh : ix->shards) fs.emplace_back(new FilterScope(sh.get(), pred));
-	const int64_t t = shard_submit(ix, Q, qdev, nq, k, nprobes, refine, L, D, C, out_host, out_host ? -1 : ix->device);
+	if (odev == -2) odev = ix->device;
+	const int64_t t = shard_submit(ix, Q, qdev, nq, k, nprobes, refine, L, D, C, out_host, out_host ? -1 : odev);
 	ix->wait_ticket(t);
 }
 

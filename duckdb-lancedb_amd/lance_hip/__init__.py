@@ -90,6 +90,13 @@ _SIGNATURES = [
     ("lance_hip_predicate_mask", i64,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_char_p, c_char_p, c_void_p, c_char_p, c_int]),
     ("lance_detached_create_scalar_index", i32, [c_void_p, c_char_p, c_char_p, c_char_p, c_int]),
+    ("lance_hip_search_batch_device_filtered", i32,
+     [c_void_p, c_void_p, i32, i32, i32, i32, i32, c_char_p, c_void_p, c_void_p, c_void_p, c_char_p, c_int]),
+    ("lance_hip_filter_prepare", i64, [c_void_p, c_char_p, c_char_p, c_int]),
+    ("lance_hip_filter_mask", i64, [c_void_p, c_char_p, c_void_p, i64, c_char_p, c_int]),
+    ("lance_hip_filter_info", i32, [c_void_p, c_void_p, i32]),
+    ("lance_hip_predicate_mask_program", i64,
+     [c_void_p, c_void_p, c_void_p, c_void_p, c_char_p, c_void_p, c_char_p, c_int]),
 ]
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
@@ -298,6 +305,82 @@ def LanceHipPredicateMask(struct_array, labels, live, predicate: str, indexed_co
     if c < 0:
         raise IOException("Lance predicate: " + e.value.decode())
     return out[:n].astype(bool)
+
+
+def LanceHipPredicateMaskProgram(struct_array, labels, live, predicate: str) -> np.ndarray:
+    """``LanceHipPredicateMask`` through the compiled predicate program and the
+    per-row interpreter the device evaluator runs (host loop, no device).
+    Raises ``IOException("Lance predicate: predicate: not device-evaluable ..")``
+    for a predicate that does not compile to a program."""
+    n = len(struct_array)
+    lab = np.ascontiguousarray(labels, np.int64)
+    lv = np.ascontiguousarray(live, np.uint8)
+    out = np.zeros(max(n, 1), np.uint8)
+    e = _err()
+    with ArrowC(struct_array) as a:
+        c = lib().lance_hip_predicate_mask_program(a.schema_ptr, a.array_ptr, lab.ctypes.data, lv.ctypes.data,
+                                                   _b(predicate), out.ctypes.data, e, ERR_BUF_LEN)
+    if c < 0:
+        raise IOException("Lance predicate: " + e.value.decode())
+    return out[:n].astype(bool)
+
+
+def LanceHipFilterPrepare(handle, predicate: str) -> int:
+    """Evaluate and cache the predicate's filter now; the selected row count."""
+    e = _err()
+    n = lib().lance_hip_filter_prepare(handle, _b(predicate), e, ERR_BUF_LEN)
+    if n < 0:
+        raise IOException("Lance filter_prepare: " + e.value.decode())
+    return int(n)
+
+
+def LanceHipFilterMask(handle, predicate: str, capacity: Optional[int] = None) -> np.ndarray:
+    """The predicate's cached filter, one bool per slot (ascending-label storage
+    order, deleted rows included)."""
+    if capacity is None:
+        info = np.zeros(6, np.int64)
+        if handle:
+            lib().lance_hip_ivf_info(handle, info.ctypes.data, 6)
+        capacity = int(info[5])
+    out = np.zeros(max(int(capacity), 1), np.uint8)
+    e = _err()
+    n = lib().lance_hip_filter_mask(handle, _b(predicate), out.ctypes.data, int(capacity), e, ERR_BUF_LEN)
+    if n < 0:
+        raise IOException("Lance filter_mask: " + e.value.decode())
+    return out[:n].astype(bool)
+
+
+def LanceHipFilterInfo(handle) -> dict:
+    out = np.zeros(7, np.int64)
+    if lib().lance_hip_filter_info(handle, out.ctypes.data, 7) != 0:
+        raise IOException("Lance filter_info: null handle")
+    return {"hits": int(out[0]), "misses": int(out[1]), "device_evals": int(out[2]), "host_evals": int(out[3]),
+            "entries": int(out[4]), "last_selected": int(out[5]), "masked_copies": int(out[6])}
+
+
+def LanceHipSearchBatchDeviceFiltered(handle, d_queries, k: int, nprobes: int = 20, refine_factor: int = 1,
+                                      predicate: Optional[str] = None, out=None):
+    """``lance_hip_search_batch_device_filtered`` over torch device tensors:
+    d_queries [nq, dim] float32 (contiguous, on the handle's device); returns
+    (labels int64 [nq, k], distances float32 [nq, k], counts int32 [nq]) device
+    tensors (``out``: such a triple to write into)."""
+    import torch
+
+    assert d_queries.dtype == torch.float32 and d_queries.is_contiguous() and d_queries.dim() == 2
+    nq, dim = d_queries.shape
+    if out is None:
+        out = (torch.empty((nq, max(k, 1)), dtype=torch.int64, device=d_queries.device),
+               torch.empty((nq, max(k, 1)), dtype=torch.float32, device=d_queries.device),
+               torch.empty(max(nq, 1), dtype=torch.int32, device=d_queries.device))
+    torch.cuda.synchronize(d_queries.device)  # the queries are ready on entry
+    e = _err()
+    n = lib().lance_hip_search_batch_device_filtered(handle, d_queries.data_ptr(), int(nq), int(dim), int(k),
+                                                     int(nprobes), int(refine_factor), _b(predicate),
+                                                     out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), e,
+                                                     ERR_BUF_LEN)
+    if n < 0:
+        raise IOException("Lance search: " + e.value.decode())
+    return out
 
 
 def LanceDetachedMerge(target, source, live_source_labels):

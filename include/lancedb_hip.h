@@ -191,16 +191,28 @@ int32_t lance_hip_device_count(void);
  *                  to a multiple of 128 (<= 1024) also keeps an int8 copy of its
  *                  rows (one scale per 256-row tile, 1 B per element + 16 B of
  *                  row terms) that the flat scans stream when there is no
- *                  predicate and no metric_quirk (any k on the threshold path of
- *                  > 65536 slots, k <= 32 on the dense path of smaller stores);
- *                  results are unchanged (exact re-rank + certificate).  Built on
- *                  the first search or by "prepare".
+ *                  metric_quirk (any k on the threshold path of > 65536 slots,
+ *                  k <= 32 on the dense path of smaller stores), with or without
+ *                  a predicate (a filtered search reads a masked copy of the row
+ *                  terms, 16 B per row); results are unchanged (exact re-rank +
+ *                  certificate).  Built on the first search or by "prepare".
  *   "prepare"      "1": build the int8 scan copy now (outside any timing)
  *   "scan_copy"    "on" (default) | "off": an f32 store may keep a bf16 copy of
- *                  its rows for the scans the int8 copy does not serve (k > 32,
- *                  a predicate, metric_quirk) and the IVF_FLAT bound scan; built
- *                  on the first search that needs it; refine and get_vector read
+ *                  its rows for the scans the int8 copy does not serve (k > 32 on
+ *                  a small store, metric_quirk, scan_i8 off) and the IVF_FLAT
+ *                  bound scan; built on the first search that needs it (a
+ *                  predicate alone never builds it); refine and get_vector read
  *                  the f32 rows, results are unchanged
+ *   "filter_eval"  "auto" (default) | "host": where a search predicate is
+ *                  evaluated on a filter-cache miss.  "auto": on the device when
+ *                  the predicate compiles to a program over numeric / boolean
+ *                  columns and `label` (csrc/meta.h), else by the host evaluator;
+ *                  "host": always the host evaluator.  Same filter either way.
+ *   "filter_cache" evaluated filters kept per handle (LRU, keyed by the exact
+ *                  predicate text, N/8 bytes of device memory each), default
+ *                  "8"; "0": every call re-evaluates.  An entry serves only the
+ *                  table state it was computed at: any add, delete, compact,
+ *                  merge or create_index makes the next use a miss.
  *   "sample_div"   the threshold sample pass covers ~1/sample_div of the row
  *                  tiles (at least 32 tiles); default "0" = auto (16 up to 8192
  *                  tiles of 256 rows, 32 past that)
@@ -299,6 +311,42 @@ int32_t lance_hip_search_batch_device(void *handle, const float *d_queries, int3
                                       int32_t nprobes, int32_t refine_factor, int64_t *d_out_labels,
                                       float *d_out_distances, int32_t *d_out_counts, char *err_buf, int err_buf_len);
 
+/* NEW — lance_hip_search_batch_device with a nullable Lance-SQL predicate (NULL
+ * or "" = exactly that call).  Synchronous; the prefilter semantics of
+ * lance_detached_search_batch (top-k over the live rows whose predicate is
+ * TRUE; with no such row every count is 0, labels -1, distances NaN); works on
+ * multi-device handles.  The predicate's filter comes from the handle's filter
+ * cache (options "filter_cache", "filter_eval"): a repeated predicate over an
+ * unchanged table costs no evaluation, no copy and no extra stream wait, and
+ * the int8 scan serves it like an unfiltered search.  Returns nq or -1.
+ * Out of scope: a predicate on lance_hip_search_batch_device_async (searches
+ * with a predicate stay synchronous), a device mirror of string columns
+ * (string predicates are evaluated on the host, then cached like any other),
+ * per-query predicates within one batch, and patching a cached filter in place
+ * after a delete (it is re-evaluated). */
+int32_t lance_hip_search_batch_device_filtered(void *handle, const float *d_queries, int32_t nq, int32_t dim,
+                                               int32_t k, int32_t nprobes, int32_t refine_factor,
+                                               const char *predicate, int64_t *d_out_labels, float *d_out_distances,
+                                               int32_t *d_out_counts, char *err_buf, int err_buf_len);
+
+/* NEW — evaluates the predicate's filter now and keeps it in the filter cache
+ * (outside any timing).  Returns the selected row count or -1. */
+int64_t lance_hip_filter_prepare(void *handle, const char *predicate, char *err_buf, int err_buf_len);
+
+/* NEW — the predicate's filter as the cache has it (evaluated first on a miss):
+ * one byte per slot, 1 = selected and live, in the ascending-label storage
+ * order with deleted rows included (as lance_hip_ivf_export lists slots).
+ * Returns the slot count, or -1 ("output buffer too small" when capacity is
+ * less; not supported on multi-device handles). */
+int64_t lance_hip_filter_mask(void *handle, const char *predicate, uint8_t *out_mask, int64_t capacity, char *err_buf,
+                              int err_buf_len);
+
+/* NEW — filter cache counters over the handle's life (first store of a
+ * multi-device handle): out[0] hits, out[1] misses, out[2] filters evaluated
+ * on the device, out[3] on the host, out[4] entries resident, out[5] selected
+ * rows of the last filter used, out[6] masked-copy kernel launches.  0 or -1. */
+int32_t lance_hip_filter_info(void *handle, int64_t *out, int32_t n);
+
 /* NEW — asynchronous device-pointer search (a serving loop that keeps the GPU
  * busy while the host prepares the next batch).  Same arguments and results as
  * lance_hip_search_batch_device, but the call only enqueues the search on the
@@ -371,6 +419,17 @@ int32_t lance_hip_merge_topk(int32_t nshard, int32_t nq, int32_t k, const int64_
 int64_t lance_hip_predicate_mask(void *arrow_schema, void *arrow_array, const int64_t *labels, const uint8_t *live,
                                  const char *predicate, const char *indexed_columns, uint8_t *out_mask, char *err_buf,
                                  int err_buf_len);
+
+/* NEW — lance_hip_predicate_mask (without indexed_columns) through the
+ * predicate program: the predicate compiled to the flat program the device
+ * evaluator runs and interpreted per row in a host loop (no device needed).
+ * The same mask and count, or -1; for a predicate that is not
+ * device-evaluable (string columns or literals, a type pairing the evaluator
+ * rejects, a program past its limits) the message begins
+ * "predicate: not device-evaluable". */
+int64_t lance_hip_predicate_mask_program(void *arrow_schema, void *arrow_array, const int64_t *labels,
+                                         const uint8_t *live, const char *predicate, uint8_t *out_mask, char *err_buf,
+                                         int err_buf_len);
 
 /* NEW — IVF state: out[0] type (-1 none, 0 IVF_FLAT, 1 IVF_PQ), out[1] nlist,
  * out[2] m, out[3] dsub, out[4] rows indexed, out[5] slots.  0 or -1. */
