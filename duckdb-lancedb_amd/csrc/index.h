@@ -342,7 +342,7 @@ struct Index {
 		filter_on = false;
 		fcur.reset();
 	}
-	int ivf_type_opt = 1;  // 0 IVF_FLAT, 1 IVF_PQ
+	int ivf_type_opt = 1;  // 0 IVF_FLAT, 1 IVF_PQ, 2 IVF_SQ
 	int kmeans_iters = 50;  // lance k-means max_iters default
 	uint64_t ivf_seed = 0x5eedULL;
 	bool pq_fast = true;    // IVF_PQ list-major 8-bit-LUT scan (option "pq_scan" = "fast"; "exact_lut": f32 LUT, query-major)

@@ -1,4 +1,4 @@
-// IVF_FLAT / IVF_PQ indexes of the MI355X-native path (internal; not public ABI).
+// IVF_FLAT / IVF_PQ / IVF_SQ indexes of the MI355X-native path (internal; not public ABI).
 //
 // Replaces what lance_manager.rs:483-515 (create_ann_index -> lancedb 0.15
 // IvfPqIndexBuilder -> lance-index 0.22 k-means + PQ training) builds and what
@@ -17,6 +17,17 @@
 //              T[l][j][c] = sum_t y_{j,c,t} * (y_{j,c,t} + 2 c_{l,j,t})
 //            (f32, t in order, no fused multiply-add); top-(k*refine_factor)
 //            by (ADC, label) -> exact re-rank -> top-k by (distance, label)
+//   IVF_SQ   model = centroids + (lo, hi), the min / max element of the k-means
+//            sample; s = (hi - lo) / 255 (1 when hi <= lo), mid = lo + 128 s; row
+//            code c = clamp(rint((v - lo) / s), 0, 255), v = x (cosine: x times
+//            the row scale 1 / |x|), stored as c' = c - 128; query qi = rint(qp /
+//            sq), sq = max|qp| / 127; I = sum qi c' (exact int32);
+//              p = (sq s) f32(I) + (sq mid) f32(sum qi)
+//              key = rt - 2 p (L2) | -p (dot, cosine), then + 0
+//              rt = (f32(dim) (mid mid) + (2 mid s) f32(sum c')) + (s s) f32(sum c'^2)
+//            every step one f32 rounding, no fused multiply-add; top-(k *
+//            refine_factor) by (key, label) -> exact re-rank -> top-k by
+//            (distance, label); restated by tests/sq_ref.py
 //   rows added after the build (slots >= n_indexed) are searched exactly and
 //   merged (LanceDB searches unindexed fragments flat); cosine works in the
 //   row-normalised space (k-means, residuals, P), exact cosine at the end.
@@ -25,7 +36,7 @@
 
 namespace lhip {
 
-enum IvfType : int { IVF_FLAT = 0, IVF_PQ = 1 };
+enum IvfType : int { IVF_FLAT = 0, IVF_PQ = 1, IVF_SQ = 2 };
 constexpr int PQ_K = 256;          // 8-bit codes (nbits = 8)
 constexpr int PQ_MAX_M = 128;      // LUT of m x 256 f32 must fit in LDS with the top-k buffer
 constexpr int PQ_MAX_DSUB = 64;    // codebook slice of one sub-space in LDS
@@ -69,6 +80,15 @@ struct IvfState {
 	bool lrows_ok = false;
 	DevBuf<int64_t> blk_pos0;
 	int nblk = 0, maxb = 1;
+	// IVF_SQ: the model's bounds and what follows from them, the list-order int8
+	// codes c - 128 [npos + 256][ldc] (zero padded, ldc = round_up(dim, 64)) and
+	// the L2 row terms [npos + 256], both rebuilt with the layout from the stored rows
+	float sq_lo = 0.f, sq_hi = 0.f, sq_s = 1.f, sq_mid = 0.f;
+	int ldc = 0;
+	DevBuf<int8_t> sqcodes;
+	DevBuf<float> sqrt_;
+	DevBuf<int8_t> sqQi;     // search: int8 queries [nq][ldc]
+	DevBuf<float2> sqpar;    // search: (sq s, sq mid sum qi) per query
 	// search workspace
 	DevBuf<float> Qf, Qn, P, probe_d, tmpf;
 	DevBuf<double> Qd, qn2;
@@ -120,7 +140,8 @@ void launch_coarse_search(const float *Q, int nq, int dim, const float *C, int l
 // take LanceDB's defaults (sqrt(rows); dim/16, dim/8 or 1).
 void ivf_build(Index *ix, int type, int num_partitions, int num_sub_vectors);
 // Install a given model (multi-GPU: rank 0 trains, every rank indexes its own
-// shard with the same centroids / codebook).  codebook may be null for IVF_FLAT.
+// shard with the same centroids / codebook).  codebook may be null for IVF_FLAT;
+// for IVF_SQ it holds the two bounds (lo, hi) and m is ignored.
 void ivf_set_model(Index *ix, int type, int nlist, int m, const float *centroids, const float *codebook);
 // lance_detached_compact (= optimize(All)): index the rows added since the build.
 void ivf_optimize(Index *ix);
@@ -132,8 +153,10 @@ void ivf_search(Index *ix, const float *dQ, int nq, int k, int nprobes, int refi
                 PendingPass *defer = nullptr);
 void ivf_finish(Index *ix, PendingPass &p);
 
-// Host copies of the model (centroids [nlist][dim], codebook [m][256][dsub]) and
-// of the per-slot list / codes (slots >= n_indexed: list -1, codes 0).
+// Host copies of the model (centroids [nlist][dim], codebook [m][256][dsub];
+// IVF_SQ: codebook = (lo, hi)) and of the per-slot list / codes (slots >=
+// n_indexed: list -1, codes 0; IVF_SQ: [slots][dim] codes c in 0 .. 255,
+// encoded on demand from the stored rows).
 void ivf_export_model(Index *ix, float *centroids, float *codebook);
 void ivf_export_slots(Index *ix, int32_t *slot_list, uint8_t *slot_codes);
 
@@ -259,5 +282,23 @@ void launch_keys_to_output(const uint64_t *keys, int nq, int K, int k, const int
                            float *outD, int *outC, hipStream_t st, int tie_desc);
 void launch_ivf_refine_final(const StoreView &s, const float *Qf, const uint64_t *ca, int ka, const uint64_t *cb,
                              int kb, int nq, int k, int64_t *outL, float *outD, int *outC, hipStream_t st);
+
+
+// ---- IVF_SQ kernel launchers (sq_kernels.hip) --------------------------------
+// out[0] / out[1] = ordered keys (fkey) of the min / max over the dim real elements of n rows of S
+void launch_sq_minmax(const float *S, int64_t n, int ld, int dim, uint32_t *out, hipStream_t st);
+// SQ codes of the rows at lslot[p] (slot p when null), c - shift, row stride ldo,
+// zero for elements dim .. padto; rt (nullable): the L2 row terms
+void launch_sq_encode(const void *X, int xbf16, int ld, int dim, const float *rowaux_f, int normalize,
+                      const uint32_t *lslot, int64_t npos, float lo, float s, float mid, int shift, int ldo, int padto,
+                      uint8_t *out, float *rt, hipStream_t st);
+// int8 queries Qi [nq][ldc] and par [nq] = (sq s, (sq mid) f32(sum qi)) of Qp [nq][qld]
+void launch_sq_query_prep(const float *Qp, int qld, int nq, int dim, int ldc, float s, float mid, int8_t *Qi,
+                          float2 *par, hipStream_t st);
+// per (query, block) four sorted runs of ko = min(kk, 64) (key, slot) words: out [pair][maxb][4 ko]
+void launch_sq_list_scan(int metric, const int8_t *lcodes, int ldc, const float *lrt, const float4 *rowaux,
+                         const int *blk_list, const int64_t *blk_pos0, const int *lblk0, const int64_t *loff,
+                         const uint32_t *lslot, int nblk, const int *pstart, const int *pairs, int nprobe, int maxb,
+                         const int8_t *Qi, const float2 *qpar, int ko, uint64_t *out, hipStream_t st);
 
 }  // namespace lhip

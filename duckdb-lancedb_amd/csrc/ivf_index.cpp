@@ -1,5 +1,6 @@
-// IVF_FLAT / IVF_PQ host side: training, indexing, list layout and the search
-// orchestration over the kernels of ivf_kernels.hip (contract in ivf.h).
+// IVF_FLAT / IVF_PQ / IVF_SQ host side: training, indexing, list layout and the search
+// orchestration over the kernels of ivf_kernels.hip and sq_kernels.hip (contract
+// in ivf.h).
 //
 // Reference behaviour restated (paths relative to /root/reference):
 //   rust_lib/src/lance_manager.rs:483-515  create_ann_index: IVF_PQ with the
@@ -10,6 +11,10 @@
 //       PQ distance, re-rank the top k*r exactly
 //   rust_lib/src/lance_manager.rs:557-561  compact = optimize(All): rows added
 //       after the build join the existing partitions
+//   rust_lib/src/lance_manager.rs:517-551  create_hnsw_index: IvfHnswSqIndexBuilder
+//       (IVF over 8-bit scalar-quantised rows, an HNSW graph per partition); here
+//       IVF_SQ, whose list scan visits every row of a probed partition by the
+//       same SQ distance (the graph itself is not built)
 //   src/lance_index.hpp:91-92              nprobes 20 / refine_factor 1 defaults
 // LanceDB-side defaults restated from lancedb 0.15 / lance-index 0.22 (not in
 // the container): num_partitions = sqrt(rows), num_sub_vectors = dim/16 (or
@@ -204,7 +209,9 @@ static void index_tail(Index *ix) {
 }
 
 // install a model given as device buffers (centroids [nlist][ld], codebook)
-static void install_model(Index *ix, int type, int nlist, int m, const float *dC, const float *dcb) {
+// IVF_SQ: sqb = the two bounds (lo, hi) on the host
+static void install_model(Index *ix, int type, int nlist, int m, const float *dC, const float *dcb,
+                          const float *sqb = nullptr) {
 	hipStream_t st = ix->stream;
 	auto s = std::make_unique<IvfState>();
 	s->type = type;
@@ -214,6 +221,17 @@ static void install_model(Index *ix, int type, int nlist, int m, const float *dC
 		s->m = m;
 		s->dsub = ix->dim / m;
 		s->mp = (int)round_up(m, 16);
+	}
+	if (type == IVF_SQ) {
+		if (!sqb || !std::isfinite(sqb[0]) || !std::isfinite(sqb[1])) throw Error("IVF_SQ bounds (lo, hi) must be finite");
+		s->m = ix->dim;  // code bytes per row
+		s->dsub = 1;
+		s->ldc = (int)round_up(ix->dim, 64);
+		s->sq_lo = sqb[0];
+		s->sq_hi = sqb[1];
+		s->sq_s = sqb[1] <= sqb[0] ? 1.0f : (sqb[1] - sqb[0]) / 255.0f;
+		if (!(s->sq_s > 0.0f) || !std::isfinite(s->sq_s)) s->sq_s = 1.0f;  // (underflow / overflow of the step)
+		s->sq_mid = sqb[0] + 128.0f * s->sq_s;  // (128 s is exact: one rounding with or without contraction)
 	}
 	s->centroids.need((size_t)nlist * ix->ld);
 	HIPCHK(hipMemcpyAsync(s->centroids.p, dC, (size_t)nlist * ix->ld * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -310,13 +328,35 @@ void ivf_build(Index *ix, int type, int num_partitions, int num_sub_vectors) {
 		cb.need((size_t)m * PQ_K * (dim / m));
 		pq_train(R.p, nR, ld, m, dim / m, ix->kmeans_iters, cb.p, sb, st);
 	}
+	float sqb[2] = {0.f, 0.f};
+	if (type == IVF_SQ) {
+		// bounds: the min / max element of the (row-normalised for cosine) sample
+		DevBuf<uint32_t> mm;
+		mm.need(2);
+		launch_sq_minmax(S.p, nS, ld, dim, mm.p, st);
+		HIPCHK(hipGetLastError());
+		uint32_t h[2];
+		HIPCHK(hipMemcpyAsync(h, mm.p, sizeof(h), hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+		auto unkey = [](uint32_t k) {
+			const uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
+			float f;
+			memcpy(&f, &u, sizeof(f));
+			return f;
+		};
+		if (h[0] > h[1]) throw Error("IVF_SQ training: the sample has no finite element");
+		sqb[0] = unkey(h[0]);
+		sqb[1] = unkey(h[1]);
+		if (!std::isfinite(sqb[0]) || !std::isfinite(sqb[1])) throw Error("IVF_SQ training: the sample has an infinite element");
+	}
 	HIPCHK(hipStreamSynchronize(st));
-	install_model(ix, type, nlist, m, C.p, type == IVF_PQ ? cb.p : nullptr);
+	install_model(ix, type, nlist, m, C.p, type == IVF_PQ ? cb.p : nullptr, sqb);
 }
 
 void ivf_set_model(Index *ix, int type, int nlist, int m, const float *centroids, const float *codebook) {
 	check_params(ix, type, nlist, m);
 	if (type == IVF_PQ && !codebook) throw Error("IVF_PQ model needs a codebook");
+	if (type == IVF_SQ && !codebook) throw Error("IVF_SQ model needs its bounds (lo, hi) in codebook");
 	hipStream_t st = ix->stream;
 	DevBuf<float> C, cb;
 	C.need((size_t)nlist * ix->ld);
@@ -329,7 +369,7 @@ void ivf_set_model(Index *ix, int type, int nlist, int m, const float *centroids
 		HIPCHK(hipMemcpyAsync(cb.p, codebook, ncb * sizeof(float), hipMemcpyHostToDevice, st));
 	}
 	HIPCHK(hipStreamSynchronize(st));
-	install_model(ix, type, nlist, m, C.p, type == IVF_PQ ? cb.p : nullptr);
+	install_model(ix, type, nlist, m, C.p, type == IVF_PQ ? cb.p : nullptr, type == IVF_SQ ? codebook : nullptr);
 }
 
 void ivf_optimize(Index *ix) {
@@ -392,7 +432,7 @@ static void layout(Index *ix) {
 	s->lslot.need(ls.size());
 	HIPCHK(hipMemcpyAsync(s->loff.p, s->h_loff.data(), ((size_t)nl + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
 	HIPCHK(hipMemcpyAsync(s->lslot.p, ls.data(), ls.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-	if (s->type == IVF_FLAT) {
+	if (s->type == IVF_FLAT || s->type == IVF_SQ) {
 		std::vector<int> bl, l0((size_t)nl + 1);
 		std::vector<int64_t> bp;
 		int maxb = 1;
@@ -420,7 +460,19 @@ static void layout(Index *ix) {
 		// the bound scan's rows in list order (+ one item of zero rows past the
 		// end: the last item reads 256 positions); rebuilt with the layout
 		s->lrows_ok = false;
-		if (ix->ivf_flat_bound && ix->ld % 64 == 0) {
+		if (s->type == IVF_SQ) {
+			// list-order codes c - 128 and L2 row terms from the stored rows (+ one item
+			// of zero rows past the end: the last item reads 256 positions)
+			const size_t rows = (size_t)npos + FLAT_BLK;
+			s->sqcodes.need(rows * s->ldc);
+			s->sqrt_.need(rows);
+			HIPCHK(hipMemsetAsync(s->sqcodes.p + (size_t)npos * s->ldc, 0, (size_t)FLAT_BLK * s->ldc, st));
+			HIPCHK(hipMemsetAsync(s->sqrt_.p + npos, 0, (size_t)FLAT_BLK * sizeof(float), st));
+			launch_sq_encode(ix->X, ix->xbf16 ? 1 : 0, ix->ld, ix->dim, reinterpret_cast<const float *>(ix->rowaux),
+			                 s->metric == METRIC_COSINE ? 1 : 0, s->lslot.p, npos, s->sq_lo, s->sq_s, s->sq_mid, 128, s->ldc,
+			                 s->ldc, reinterpret_cast<uint8_t *>(s->sqcodes.p), s->sqrt_.p, st);
+			HIPCHK(hipGetLastError());
+		} else if (ix->ivf_flat_bound && ix->ld % 64 == 0) {
 			const size_t rows = (size_t)npos + FLAT_BLK;
 			s->lrows.need(rows * ix->ld);
 			HIPCHK(hipMemsetAsync(s->lrows.p + (size_t)npos * ix->ld, 0, (size_t)FLAT_BLK * ix->ld * sizeof(uint16_t), st));
@@ -454,7 +506,7 @@ static void layout(Index *ix) {
 
 // time_kernels: the list-scan launch (events 0/1 on the handle's stream) and
 // its algorithmic work: every probed list's rows once (IVF_FLAT: dim x esz
-// bytes; IVF_PQ: m code bytes + the 4-B row term tau for L2 / cosine) plus, for
+// bytes; IVF_SQ (esz < 0): ldc code bytes + the 4-B row term; IVF_PQ: m code bytes + the 4-B row term tau for L2 / cosine) plus, for
 // IVF_PQ, each query's LUT (m x 256 entries: f32 P[q], or the fast scan's
 // 8-bit table) once; pair rows = sum over
 // (query, list) pairs of the list's rows.
@@ -468,7 +520,7 @@ static void account_list_scan(Index *ix, int esz, int nq, int lut_bytes) {
 		const int np = ps[(size_t)l + 1] - ps[(size_t)l];
 		if (np <= 0) continue;
 		const double rows = (double)s->h_lcnt[(size_t)l];
-		bytes += esz ? rows * ix->dim * esz : rows * row_pq;
+		bytes += esz < 0 ? rows * (s->ldc + 4.0) : esz ? rows * ix->dim * esz : rows * row_pq;
 		pair_rows += rows * np;
 	}
 	ix->kt_ivf_ms += ix->toc_ms(0, 1);
@@ -494,7 +546,11 @@ void ivf_search(Index *ix, const float *dQ, int nq, int k, int nprobes, int refi
 	StoreView sv = store_view(ix);
 	sv.rowaux = ix->search_aux(ix->rowaux);  // filtered search: unselected slots read as tombstones
 	// queries per pass: bounded by MAX_PASS_Q and ~1 GiB of list-scan keys
+	if (s->type == IVF_SQ && (int64_t)k * rf > IVF_MAX_K)
+		throw Error("k * refine_factor > " + std::to_string(IVF_MAX_K) + " is not supported by the IVF_SQ path");
+	const int sq_ko = std::min(kp, 64);  // IVF_SQ: keys per 64-row run of a (query, item)
 	const int64_t per_q = s->type == IVF_FLAT ? (int64_t)nprobe * s->maxb * kk + (int64_t)tail_nb * kk
+	                      : s->type == IVF_SQ ? (int64_t)nprobe * s->maxb * 4 * sq_ko + (int64_t)tail_nb * kk
 	                                          : (int64_t)32 * kp + (int64_t)tail_nb * kk;
 	const int pass = (int)std::max<int64_t>(1, std::min<int64_t>(MAX_PASS_Q, (int64_t)(1 << 27) / std::max<int64_t>(per_q, 1)));
 	const bool fast_pq = s->type == IVF_PQ && ix->pq_fast && s->m <= FQ_MAX_M && kp <= FQ_MAX_KK;
@@ -631,6 +687,28 @@ void ivf_search(Index *ix, const float *dQ, int nq, int k, int nprobes, int refi
 				launch_keys_to_output(s->cand_a.p, n, k, k, ix->dlabels, oL, oD, oC, st, ix->tie_desc);
 			} else if (s->type == IVF_FLAT) {
 				// bound scan certified every query of the pass
+			} else if (s->type == IVF_SQ) {
+				// int8 queries -> MFMA list scan (per (query, item) sorted runs of SQ keys) ->
+				// per-query top-kp by (key, slot) -> exact re-rank with the tail's candidates
+				s->sqQi.need((size_t)n * s->ldc);
+				s->sqpar.need((size_t)n);
+				launch_sq_query_prep(cos ? s->Qn.p : s->Qf.p, cos ? dim : ld, n, dim, s->ldc, s->sq_s, s->sq_mid, s->sqQi.p,
+				                     s->sqpar.p, st);
+				s->keys.need((size_t)n * nprobe * s->maxb * 4 * sq_ko);
+				ix->tic(0);
+				launch_sq_list_scan(s->metric, s->sqcodes.p, s->ldc, s->sqrt_.p, sv.rowaux, s->blk_list.p, s->blk_pos0.p,
+				                    s->lblk0.p, s->loff.p, s->lslot.p, s->nblk, s->pstart.p, s->pairs.p, nprobe, s->maxb,
+				                    s->sqQi.p, s->sqpar.p, sq_ko, s->keys.p, st);
+				ix->tic(1);
+				s->cand_a.need((size_t)n * kp);
+				launch_ivf_merge(n, nprobe, s->probe_l.p, s->lblk0.p, s->maxb, 4 * sq_ko, s->keys.p, 0, nullptr, kp,
+				                 s->cand_a.p, st);
+				if (tail_n > 0) {
+					s->cand_b.need((size_t)n * k);
+					launch_ivf_merge(n, 0, nullptr, nullptr, 1, kk, nullptr, tail_nb, s->tkeys.p, k, s->cand_b.p, st);
+				}
+				launch_ivf_refine_final(sv, s->Qf.p, s->cand_a.p, kp, tail_n > 0 ? s->cand_b.p : nullptr,
+				                        tail_n > 0 ? k : 0, n, k, oL, oD, oC, st);
 			} else if (ix->pq_fast && s->m <= FQ_MAX_M && kp <= FQ_MAX_KK) {
 				// list-major 8-bit-LUT scan: FQ_G queries per LUT lookup, each probed
 				// list's codes streamed once per query group
@@ -748,7 +826,8 @@ void ivf_search(Index *ix, const float *dQ, int nq, int k, int nprobes, int refi
 				}
 			}
 			if (ix->time_kernels && !(s->type == IVF_FLAT && lb_flat && !exact_flat))
-				account_list_scan(ix, s->type == IVF_FLAT ? (ix->xbf16 ? 2 : 4) : 0, n, fast_pq ? 1 : 4);
+				account_list_scan(ix, s->type == IVF_FLAT ? (ix->xbf16 ? 2 : 4) : s->type == IVF_SQ ? -1 : 0, n,
+				                  fast_pq ? 1 : 4);
 			break;
 		}
 	}
@@ -802,6 +881,7 @@ static void model_host(Index *ix, std::vector<float> &C, std::vector<float> &cb)
 		cb.resize((size_t)s->m * PQ_K * s->dsub);
 		HIPCHK(hipMemcpy(cb.data(), s->codebook.p, cb.size() * sizeof(float), hipMemcpyDeviceToHost));
 	}
+	if (s->type == IVF_SQ) cb = {s->sq_lo, s->sq_hi};
 }
 
 void ivf_export_model(Index *ix, float *centroids, float *codebook) {
@@ -820,7 +900,18 @@ void ivf_export_slots(Index *ix, int32_t *slot_list, uint8_t *slot_codes) {
 		for (int64_t i = 0; i < n; ++i) slot_list[i] = i < ni ? a[(size_t)i] : -1;
 	}
 	if (slot_codes) {
-		memset(slot_codes, 0, (size_t)n * (s->type == IVF_PQ ? s->m : 0));
+		memset(slot_codes, 0, (size_t)n * (s->type == IVF_FLAT ? 0 : s->m));
+		if (s->type == IVF_SQ && ni > 0) {
+			// encoded on demand from the stored rows (no slot-major copy is kept)
+			DevBuf<uint8_t> c;
+			c.need((size_t)ni * ix->dim);
+			launch_sq_encode(ix->X, ix->xbf16 ? 1 : 0, ix->ld, ix->dim, reinterpret_cast<const float *>(ix->rowaux),
+			                 s->metric == METRIC_COSINE ? 1 : 0, nullptr, ni, s->sq_lo, s->sq_s, s->sq_mid, 0, ix->dim,
+			                 ix->dim, c.p, nullptr, ix->stream);
+			HIPCHK(hipGetLastError());
+			HIPCHK(hipStreamSynchronize(ix->stream));
+			HIPCHK(hipMemcpy(slot_codes, c.p, (size_t)ni * ix->dim, hipMemcpyDeviceToHost));
+		}
 		if (s->type == IVF_PQ && ni > 0) {
 			std::vector<uint8_t> c((size_t)ni * s->mp);
 			HIPCHK(hipMemcpy(c.data(), s->codes.p, c.size(), hipMemcpyDeviceToHost));

@@ -719,9 +719,13 @@ static void replay_log(Index *ix, const std::string &path) {
 				cb.resize((size_t)m * PQ_K * (d / m));
 				if (fread(cb.data(), sizeof(float), cb.size(), f) != cb.size()) break;
 			}
+			if (type == IVF_SQ) {  // the two bounds (lo, hi)
+				cb.resize(2);
+				if (fread(cb.data(), sizeof(float), 2, f) != 2) break;
+			}
 			for (Index *t : all) {
 				if (ix->sharded()) t->bind();
-				ivf_set_model(t, type, nl, m, C.data(), type == IVF_PQ ? cb.data() : nullptr);
+				ivf_set_model(t, type, nl, m, C.data(), cb.empty() ? nullptr : cb.data());
 			}
 		} else if (tag == 5) {
 			for (Index *t : all) {
@@ -1386,7 +1390,25 @@ int32_t lance_detached_create_hnsw_index(void *handle, int32_t m, int32_t ef_con
 		lhip::write_err(err_buf, err_buf_len, "null handle");
 		return -1;
 	}
-	return 0;
+	// IvfHnswSqIndexBuilder (lance_manager.rs:517-551) -> IVF_SQ with LanceDB's default
+	// sqrt(rows) partitions, whatever the index_type option says; the per-partition
+	// graph is not built (the list scan visits every row of a probed partition), so
+	// m and ef_construction are accepted and unused
+	(void)m;
+	(void)ef_construction;
+	try {
+		Index *ix = as_index(handle);
+		std::lock_guard<std::mutex> g(ix->mu);
+		ix->bind();
+		if (ix->sharded()) {
+			lhip::shard_create_index(ix, lhip::IVF_SQ, 0, 0);
+			return 0;
+		}
+		lhip::ivf_build(ix, lhip::IVF_SQ, 0, 0);
+		ix->log_model();
+		return 0;
+	}
+	API_GUARD("create_hnsw_index failed: ", -1)
 }
 
 int32_t lance_detached_compact(void *handle, char *err_buf, int err_buf_len) {
@@ -1630,8 +1652,10 @@ static void set_option_store(Index *ix, const std::string &k, const std::string 
 			ix->ivf_type_opt = lhip::IVF_PQ;
 		else if (v == "ivf_flat" || v == "IVF_FLAT")
 			ix->ivf_type_opt = lhip::IVF_FLAT;
+		else if (v == "ivf_sq" || v == "IVF_SQ")
+			ix->ivf_type_opt = lhip::IVF_SQ;
 		else
-			throw Error("index_type must be 'ivf_pq' or 'ivf_flat'");
+			throw Error("index_type must be 'ivf_pq', 'ivf_flat' or 'ivf_sq'");
 		return;
 	}
 	if (k == "kmeans_iters") {
@@ -2170,7 +2194,10 @@ int32_t lance_hip_ivf_set_model(void *handle, int32_t index_type, int32_t num_pa
 	try {
 		Index *ix = as_index(handle);
 		std::lock_guard<std::mutex> g(ix->mu);
-		if (index_type != lhip::IVF_FLAT && index_type != lhip::IVF_PQ) throw Error("index_type must be 0 or 1");
+		if (index_type != lhip::IVF_FLAT && index_type != lhip::IVF_PQ && index_type != lhip::IVF_SQ)
+			throw Error("index_type must be 0, 1 or 2");
+		if (index_type == lhip::IVF_SQ && (!codebook || !std::isfinite(codebook[0]) || !std::isfinite(codebook[1])))
+			throw Error("IVF_SQ needs two finite bounds (lo, hi) in codebook");
 		if (!centroids) throw Error("null centroids");
 		ix->bind();
 		if (ix->sharded()) {

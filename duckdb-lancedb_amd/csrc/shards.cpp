@@ -438,6 +438,7 @@ void shard_create_index(Index *ix, int type, int num_partitions, int num_sub_vec
 	const int nl = tr->ivf->nlist, mm = tr->ivf->m;
 	std::vector<float> C((size_t)nl * dim), cb;
 	if (type == IVF_PQ) cb.resize((size_t)mm * PQ_K * (dim / mm));
+	if (type == IVF_SQ) cb.resize(2);  // the bounds (lo, hi)
 	ivf_export_model(tr, C.data(), cb.empty() ? nullptr : cb.data());
 	for (auto &s : ix->shards) {
 		if (s.get() == tr) continue;

@@ -522,12 +522,12 @@ def LanceHipKernelTimes(handle) -> dict:
             "scan_kernel": {2: "scan8_kernel"}.get(int(out[12]), "scan_kernel")}
 
 
-IVF_TYPES = {-1: None, 0: "ivf_flat", 1: "ivf_pq"}
+IVF_TYPES = {-1: None, 0: "ivf_flat", 1: "ivf_pq", 2: "ivf_sq"}
 
 
 def LanceHipIvfInfo(handle) -> dict:
     """IVF state of a handle: type (None when the table has no index), nlist,
-    m (sub-vectors), dsub, rows indexed, slots."""
+    m (sub-vectors; IVF_SQ: code bytes per row = dim), dsub, rows indexed, slots."""
     out = np.zeros(6, np.int64)
     lib().lance_hip_ivf_info(handle, out.ctypes.data, 6)
     return {"type": IVF_TYPES[int(out[0])], "nlist": int(out[1]), "m": int(out[2]), "dsub": int(out[3]),
@@ -536,8 +536,9 @@ def LanceHipIvfInfo(handle) -> dict:
 
 def LanceHipIvfExport(handle) -> dict:
     """Host copy of the IVF model and of the per-slot layout (for the oracle):
-    centroids [nlist, dim], codebook [m, 256, dsub] (IVF_PQ), and per slot:
-    label, live flag, list (-1 = not indexed yet), codes [m]."""
+    centroids [nlist, dim], codebook [m, 256, dsub] (IVF_PQ) or the two bounds
+    (lo, hi) (IVF_SQ), and per slot: label, live flag, list (-1 = not indexed
+    yet), codes [m] (IVF_SQ: the dim unshifted 8-bit codes of the row)."""
     info = LanceHipIvfInfo(handle)
     if info["type"] is None:
         raise IOException("Lance ivf_export: no IVF index")
@@ -545,28 +546,29 @@ def LanceHipIvfExport(handle) -> dict:
     ns = info["n_slots"]
     C = np.zeros((info["nlist"], dim), np.float32)
     pq = info["type"] == "ivf_pq"
-    cb = np.zeros((info["m"], 256, info["dsub"]), np.float32) if pq else None
+    sq = info["type"] == "ivf_sq"
+    cb = np.zeros((info["m"], 256, info["dsub"]), np.float32) if pq else np.zeros(2, np.float32) if sq else None
     labels = np.zeros(ns, np.int64)
     live = np.zeros(ns, np.uint8)
     lists = np.zeros(ns, np.int32)
     codes = np.zeros((ns, max(info["m"], 1)), np.uint8)
     e = _err()
-    r = lib().lance_hip_ivf_export(handle, C.ctypes.data, cb.ctypes.data if pq else None, labels.ctypes.data,
-                                   live.ctypes.data, lists.ctypes.data, codes.ctypes.data if pq else None, e,
+    r = lib().lance_hip_ivf_export(handle, C.ctypes.data, cb.ctypes.data if pq or sq else None, labels.ctypes.data,
+                                   live.ctypes.data, lists.ctypes.data, codes.ctypes.data if pq or sq else None, e,
                                    ERR_BUF_LEN)
     if r != 0:
         raise IOException("Lance ivf_export: " + e.value.decode())
     return {**info, "centroids": C, "codebook": cb, "labels": labels, "live": live.astype(bool), "lists": lists,
-            "codes": codes if pq else None}
+            "codes": codes if pq or sq else None}
 
 
 def LanceHipIvfSetModel(handle, index_type: str, centroids, codebook=None) -> None:
     """Install a trained IVF model (rank 0's, on every rank) and index this
-    handle's rows with it."""
+    handle's rows with it.  IVF_SQ: codebook is the length-2 array (lo, hi)."""
     C = np.ascontiguousarray(centroids, dtype=np.float32)
-    t = {"ivf_flat": 0, "ivf_pq": 1}[index_type]
+    t = {"ivf_flat": 0, "ivf_pq": 1, "ivf_sq": 2}[index_type]
     cb = None if codebook is None else np.ascontiguousarray(codebook, dtype=np.float32)
-    m = 0 if cb is None else cb.shape[0]
+    m = 0 if cb is None or t == 2 else cb.shape[0]
     e = _err()
     r = lib().lance_hip_ivf_set_model(handle, t, C.shape[0], m, C.ctypes.data, None if cb is None else cb.ctypes.data,
                                       e, ERR_BUF_LEN)

@@ -126,7 +126,8 @@ int32_t lance_detached_delete_batch(void *handle, const int64_t *labels, int32_t
 
 /* ffi.rs:403-423 (rust_ffi.cpp:168), lance_manager.rs:483-515.  Trains and
  * builds an IVF index over the live rows (replace = true): IVF_PQ (default, as
- * the reference builds) or IVF_FLAT (option "index_type").  num_partitions /
+ * the reference builds), IVF_FLAT or IVF_SQ (option "index_type"; IVF_SQ ignores
+ * num_sub_vectors).  num_partitions /
  * num_sub_vectors <= 0 take LanceDB's defaults (sqrt(rows); dim/16, dim/8 or 1).
  * Later searches probe `nprobes` partitions and re-rank k*refine_factor PQ
  * candidates exactly; rows added afterwards are searched exactly until
@@ -142,9 +143,16 @@ int32_t lance_detached_create_index(void *handle, int32_t num_partitions, int32_
 int32_t lance_detached_create_scalar_index(void *handle, const char *column, const char *index_type, char *err_buf,
                                            int err_buf_len);
 
-/* ffi.rs:425-445 (rust_ffi.cpp:176).  HNSW is out of scope:
- * returns 0 and keeps serving exact flat search (lance_hnsw.test pins only
- * result counts). */
+/* ffi.rs:425-445 (rust_ffi.cpp:176), lance_manager.rs:517-551
+ * (IvfHnswSqIndexBuilder: IVF over 8-bit scalar-quantised rows, an HNSW graph
+ * per partition).  Builds an IVF_SQ index over the live rows (replace = true)
+ * with LanceDB's default sqrt(rows) partitions, whatever the "index_type" option
+ * says: every row of a probed partition is ranked by the same scalar-quantised
+ * distance the graph would use (an int8 MFMA list scan), the best
+ * k * refine_factor are re-ranked exactly.  The per-partition graph itself is
+ * not built: m and ef_construction are accepted (any value) and unused.  Works
+ * on multi-device handles; the model is persisted in the table log.  0, or -1
+ * with "create_hnsw_index failed: ..." (an empty table is an error). */
 int32_t lance_detached_create_hnsw_index(void *handle, int32_t m, int32_t ef_construction, char *err_buf,
                                           int err_buf_len);
 
@@ -230,7 +238,8 @@ int32_t lance_hip_device_count(void);
  *                  distances + merge instead of the bound/refine pipeline
  *   "retry_pass"   "1" (default) | "0": rerun uncertified threshold-path
  *                  queries with a tightened tau before the exact fallback
- *   "index_type"   "ivf_pq" (default) | "ivf_flat": what create_index builds
+ *   "index_type"   "ivf_pq" (default) | "ivf_flat" | "ivf_sq": what create_index
+ *                  builds (create_hnsw_index always builds IVF_SQ)
  *   "kmeans_iters" k-means iterations (coarse and PQ), default "50"
  *   "ivf_seed"     seed of the k-means training sample, default 24301
  *   "ivf_flat_scan" "bound" (default) | "exact": IVF_FLAT list scan by MFMA bf16
@@ -359,7 +368,7 @@ int32_t lance_hip_filter_info(void *handle, int64_t *out, int32_t n);
  * options (search, add, delete, compact, create_index, get_vector,
  * lance_hip_set_option, ...) first completes every pending one; count,
  * dimension and the statistics getters only read host state.  An IVF search
- * that fits one pass (<= 2048 queries) is enqueued whole (round 6; its
+ * that fits one pass (<= 2048 queries) is enqueued whole (IVF_SQ included; its
  * coarse-search flags and any rerun at the wait); flat searches that are not a single
  * threshold-path pass (small stores, > 2048 queries) and every search with a
  * predicate or option time_kernels run synchronously inside the call. */
@@ -431,21 +440,26 @@ int64_t lance_hip_predicate_mask_program(void *arrow_schema, void *arrow_array, 
                                          const uint8_t *live, const char *predicate, uint8_t *out_mask, char *err_buf,
                                          int err_buf_len);
 
-/* NEW — IVF state: out[0] type (-1 none, 0 IVF_FLAT, 1 IVF_PQ), out[1] nlist,
- * out[2] m, out[3] dsub, out[4] rows indexed, out[5] slots.  0 or -1. */
+/* NEW — IVF state: out[0] type (-1 none, 0 IVF_FLAT, 1 IVF_PQ, 2 IVF_SQ), out[1]
+ * nlist, out[2] m (IVF_SQ: the code bytes per row = dim), out[3] dsub (IVF_SQ: 1),
+ * out[4] rows indexed, out[5] slots.  0 or -1. */
 int32_t lance_hip_ivf_info(void *handle, int64_t *out, int32_t n);
 
 /* NEW — host copy of the IVF model and per-slot layout (any pointer may be
  * NULL): centroids [nlist][dim], codebook [m][256][dsub], and for every slot
  * (the ascending-label storage order, deleted rows included until compaction):
- * label, live flag, list (-1 = not indexed yet), codes [m].  0 or -1. */
+ * label, live flag, list (-1 = not indexed yet), codes [m].  IVF_SQ: codebook
+ * receives the two bounds (lo, hi) and slot_codes is [slots][dim], the unshifted
+ * 8-bit code c of every element (encoded on demand from the stored rows).
+ * 0 or -1. */
 int32_t lance_hip_ivf_export(void *handle, float *centroids, float *codebook, int64_t *slot_labels,
                              uint8_t *slot_live, int32_t *slot_list, uint8_t *slot_codes, char *err_buf,
                              int err_buf_len);
 
 /* NEW — install a trained model (multi-GPU: rank 0 trains, every rank indexes
  * its shard with the same centroids / codebook).  index_type 0 IVF_FLAT, 1
- * IVF_PQ; codebook [m][256][dim/m] (NULL for IVF_FLAT).  0 or -1. */
+ * IVF_PQ, 2 IVF_SQ; codebook [m][256][dim/m] (NULL for IVF_FLAT; IVF_SQ: the two
+ * bounds (lo, hi), finite, and num_sub_vectors is ignored).  0 or -1. */
 int32_t lance_hip_ivf_set_model(void *handle, int32_t index_type, int32_t num_partitions, int32_t num_sub_vectors,
                                 const float *centroids, const float *codebook, char *err_buf, int err_buf_len);
 
